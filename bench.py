@@ -7,10 +7,11 @@ column-major) followed by the Poseidon Merkle cap (height 4) over the 2^20 bit-r
 Metric: ms per 2^20 NTT, whole job = elapsed / (steps * 135 * n_gpus); weak scaling (every GPU
 commits its own trace; the path has no data-path collective).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K steps and reports them; --full adds the CPU
+baseline with the oracle check of the first step, per-kernel times and rooflines, and the side measurements.
 """
 import argparse
 import json
@@ -27,6 +28,7 @@ LOG_N = 20
 COLS = 135
 CAP_H = 4
 SEED = 0x243F6A8885A308D3
+DUMP_SAMPLE = 1 << 20   # elements of the transformed trace that --dump-outputs writes (16 MB as float64 halves)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 # integer-VALU issue peak (MI355X_MICROARCH.md: 256 CUs x 4 SIMD-32, one wave64 VALU instruction per 2 cycles per SIMD, 2.4 GHz):
 VALU_PEAK_TLOPS = 256 * 4 * 32 * 2.4e9 / 1e12  # = 78.6 T lane-ops/s; only an all-VOP2 stream reaches it (profiles/r01_ubench_valu.txt)
@@ -133,6 +135,18 @@ def splitmix64_felts(seed, n):
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         z = z ^ (z >> np.uint64(31))
     return z % P
+
+
+def dump_outputs(out_dir, data, cap, k, n):
+    """--dump-outputs: what the last timed step hands its caller, as float64 arrays whose last axis holds the low and high
+    32-bit halves of each Goldilocks element (both exact in float64): merkle_cap.npy (2^CAP_H digests x 4 elements) and
+    trace_sample.npy, a fixed, seeded sample of the transformed 2^log_n x k trace (column-major index col * n + row, sorted)."""
+    def halves(a):
+        return np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.unique(np.random.default_rng(SEED).integers(0, k * n, size=min(DUMP_SAMPLE, k * n), dtype=np.int64))
+    np.save(os.path.join(out_dir, "merkle_cap.npy"), halves(cap.download().reshape(-1, 4)))
+    np.save(os.path.join(out_dir, "trace_sample.npy"), halves(data.download()[idx]))
 
 
 def host_cpu_share():
@@ -512,9 +526,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cols", type=int, default=COLS)
     ap.add_argument("--log-n", type=int, default=LOG_N)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-qbench", action="store_true", help="skip the side measurements (q-bench, NTT variants, Groth16 kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the CPU baseline with the oracle check of the first step, per-kernel times and rooflines, "
+                         "and the side measurements (NTT variants, power and clock, q-bench, Groth16 and STARK kernels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle check")
+    ap.add_argument("--no-qbench", action="store_true", help="with --full: skip the side measurements (q-bench, NTT variants, Groth16 kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    cpu_check = args.full and not args.no_cpu_baseline
+    side = args.full and not args.no_qbench
 
     # `python bench.py --gpus N` without a launcher: this process starts N ranks of itself (one per GPU) before anything
     # here touches the GPU, passes rank 0's JSON line through and fails when any rank fails. Under torchrun
@@ -557,13 +579,7 @@ def main():
     cap = prover.alloc(4 << CAP_H)
 
     def sync():
-        prover.sync()
-        try:
-            import torch
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()
-        except ImportError:
-            pass
+        prover.sync()   # the library issues all its work on this context's one stream
 
     def barrier():
         D.barrier(dist)
@@ -574,7 +590,7 @@ def main():
 
     # correctness gate on this rank's first step (rank 0 also times the CPU baseline with it)
     base = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and cpu_check:
         base, want_cols, want_cap = cpu_baseline(host, log_n, CAP_H)
         step()
         sync()
@@ -590,20 +606,23 @@ def main():
         step()
     sync()
     barrier()
-    prover.profile_begin()
+    if args.full:   # per-kernel HIP events around every launch of the timed steps
+        prover.profile_begin()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     sync()
     barrier()
     t1 = time.perf_counter()
-    prof = prover.profile_end()
+    prof = prover.profile_end() if args.full else None
     elapsed = D.max_over_ranks(dist, t1 - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, data, cap, k, n)
 
     # M2's other transforms: inverse NTT and the rate-8 coset LDE 2^20 -> 2^23 (shift 7), batch 16,
     # device-resident, HIP events around the whole call. Side measurement (not part of `value`).
     variants = None
-    if (k, log_n) == (COLS, LOG_N) and not args.no_qbench:
+    if (k, log_n) == (COLS, LOG_N) and side:
         vb = 16
         e0, e1 = prover.event(), prover.event()
         src = prover.alloc(vb * n)
@@ -626,14 +645,14 @@ def main():
         src.free()
         dst.free()
     pw = None
-    if rank == 0 and (k, log_n) == (COLS, LOG_N) and not args.no_qbench:
+    if rank == 0 and (k, log_n) == (COLS, LOG_N) and side:
         pw = power_and_clock(prover, cp, data.ptr, cap.ptr, k, log_n)
     data.free()
     data = None
 
     # "block proofs/sec (qbench)": every rank runs the native harness on its own GPU (jobs shard by block, no collective)
     qb = None
-    if not args.no_qbench:
+    if side:
         # the synthetic circuit pack (26 circuits, 64 witnesses, the oracle's proofs of 8 of them) is written once, by rank 0,
         # into a fresh private directory whose name the other ranks learn through the control plane
         import shutil
@@ -650,13 +669,13 @@ def main():
         qb = dict(mine)
         for key in ("blocks_per_s", "proofs_per_s", "throughput_mode_proofs_per_s"):
             qb[key] = D.sum_over_ranks(dist, mine[key])
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and cpu_check:
             qb["cpu_baseline"] = cpu_port_proof(prover, min(host_cpu_share()[0], 64))
 
     # Groth16-wrap kernels, side measurement on rank 0: G1 MSM and F_r NTT at 2^20, both with a
     # correctness check inside (closed form resp. inverse round trip) — tools/bench_msm.py, tools/bench_fr_ntt.py
     g16 = None
-    if rank == 0 and not args.no_qbench:
+    if rank == 0 and side:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_msm
         import bench_fr_ntt
@@ -705,7 +724,7 @@ def main():
     # A13's polynomial-commitment half through the generic seams (cp_batch_commit_dev / cp_fri_prove) at the SHA-256 STARK's
     # shapes, side measurement on rank 0 with cp_fri_verify as its check — tools/bench_stark_fri.py
     stark = None
-    if rank == 0 and not args.no_qbench:
+    if rank == 0 and side:
         import bench_stark_fri
         stark = {"2^10": bench_stark_fri.run(prover, 10, reps=3), "2^14": bench_stark_fri.run(prover, 14, reps=3),
                  "2^16": bench_stark_fri.run(prover, 16, reps=2)}
@@ -714,7 +733,7 @@ def main():
     # of >= 10^4 ops at the SHA-256 STARK's width evaluated on the quotient coset straight from the committed traces; the whole
     # prover with its extended columns filled on the device) - tools/bench_stark_air.py; tests/test_gpu_air.py holds the bytes
     stark_air = stark_sha = None
-    if rank == 0 and not args.no_qbench:
+    if rank == 0 and side:
         import bench_stark_air
         stark_air = {"2^10": bench_stark_air.run(prover, 10, reps=3), "2^14": bench_stark_air.run(prover, 14, reps=3),
                      "2^16": bench_stark_air.run(prover, 16, reps=2)}
@@ -725,7 +744,17 @@ def main():
         ms_step = elapsed * 1e3 / args.steps
         ntts = k * world
         value = ms_step / ntts
+        out = {
+            "metric": "ms/NTT at 2^20 Goldilocks (commit-shaped step: 135-column 2^20-row NTT + Poseidon Merkle cap)",
+            "value": value, "unit": "ms/NTT", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_step, "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u64 (Goldilocks mod 2^64-2^32+1; the Poseidon MDS layers are evaluated exactly on 32-bit limbs held in f64)", "data": "synthetic",
+            "config": {"workload": "configs[1]: 2^%d-row x %d-column trace, forward NTT per column "
+                                   "(natural->bit-reversed) + Poseidon Merkle cap height %d" % (log_n, k, CAP_H),
+                       "log_n": log_n, "columns": k, "cap_height": CAP_H, "sharding": "independent traces per GPU"},
+        }
 
+    if rank == 0 and args.full:
         def kern(name):
             d = prof.get(name)
             return (d["total_ms"] / d["launches"], d["launches"]) if d else (None, 0)
@@ -833,14 +862,7 @@ def main():
         roof_ntt["valu_issue_note"] = ("priced against VALU issue the passes are NOT idle: frac_of_mix_rate is 4 cycles per wave64 instruction (the rate of "
                                        "the quarter-rate multiply-adds the field product is made of) over the cycles a SIMD actually spent per instruction. A "
                                        "10 + 10 split of the 20 stages moves no instruction out of the kernels; what would is a cheaper butterfly (DESIGN 4.3)")
-        out = {
-            "metric": "ms/NTT at 2^20 Goldilocks (commit-shaped step: 135-column 2^20-row NTT + Poseidon Merkle cap)",
-            "value": value, "unit": "ms/NTT", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_step, "higher_is_better": False, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u64 (Goldilocks mod 2^64-2^32+1; the Poseidon MDS layers are evaluated exactly on 32-bit limbs held in f64)", "data": "synthetic",
-            "config": {"workload": "configs[1]: 2^%d-row x %d-column trace, forward NTT per column "
-                                   "(natural->bit-reversed) + Poseidon Merkle cap height %d" % (log_n, k, CAP_H),
-                       "log_n": log_n, "columns": k, "cap_height": CAP_H, "sharding": "independent traces per GPU"},
+        out.update({
             "roofline": roof, "roofline_ntt": roof_ntt, "ntt_variants": variants,
             "kernels_ms_per_step": {name: d["total_ms"] / args.steps for name, d in prof.items()},
             "poseidon_perms_per_s": (perms / (leaf_ms * 1e-3)) if leaf_ms else None,
@@ -858,7 +880,8 @@ def main():
             "stark_air": stark_air,
             "stark_sha256": stark_sha,
             "power_and_clock": pw,
-        }
+        })
+    if rank == 0:
         emit(out)
     cap.free()
     prover.close()

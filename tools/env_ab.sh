@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of one environment knob of the library on (1) the headline step (bench.py --no-qbench: ms/NTT, leaf hash, tree levels) and
+# A/B of one environment knob of the library on (1) the headline step (bench.py --full --no-qbench: ms/NTT, leaf hash, tree levels) and
 # (2) the q-bench harness (64 blocks in flight, the raw proofs/s loop, one block alone). Alternates the settings ROUNDS times on
 # the one box. usage: tools/env_ab.sh VAR "v1 v2 ..." [rounds] [out.jsonl]   (run through gpurun from the repo root)
 set -e
@@ -12,7 +12,7 @@ Q="$R/tools/cityprover_qbench"; D="$R/tests/golden/qbench_example.bin"
 : > "$OUT"
 for r in $(seq 1 $ROUNDS); do for v in $VALS; do
   export $VAR=$v
-  b=$(python3 "$R/bench.py" --no-qbench --steps 20 --warmup 3 2>/dev/null | tail -1 | python3 -c "
+  b=$(python3 "$R/bench.py" --full --no-qbench --steps 20 --warmup 3 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernels_ms_per_step']
