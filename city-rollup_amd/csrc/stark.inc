@@ -126,10 +126,27 @@ int air_points_per_lane(cp_ctx *ctx) {
   return v >= 4 ? 4 : v >= 2 ? 2 : 1;
 }
 
+// shared memory a workgroup of this context's device may ask for (160 KiB per CU on gfx950, but ask the device)
+int device_lds_per_block(cp_ctx *ctx, size_t &out) {
+  if (!ctx->lds_per_block) {
+    int v = 0;
+    HIP_TRY(ctx, hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+    if (v <= 0) return set_error(ctx, CP_ERR_HIP, "the device reports no shared memory per workgroup");
+    ctx->lds_per_block = (size_t)v;
+  }
+  out = ctx->lds_per_block;
+  return CP_OK;
+}
+
 int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::Variant &V, air::KArgs &ka, int K) {
   const uint32_t S = V.C.n_segments();
   const size_t blocks = (ka.M + (size_t)air::WAVE * K - 1) / ((size_t)air::WAVE * K);
-  const uint32_t n_lds = std::min(V.C.n_slots, air_lds_slots(ctx)), n_spill = V.C.n_slots - n_lds;
+  // a slot takes K x 64 x 8 B of the workgroup's (one wave's) LDS: at most as many slots in LDS as the device grants a workgroup
+  size_t lds_max = 0;
+  CP_TRY(device_lds_per_block(ctx, lds_max));
+  const uint32_t lds_fit = (uint32_t)std::min<size_t>(lds_max / ((size_t)K * air::WAVE * 8), air::DST_NONE);
+  if (lds_fit < 1) return set_error(ctx, CP_ERR_UNSUPPORTED, "one AIR slot (%zu B) exceeds the device's %zu B of LDS per workgroup", (size_t)K * air::WAVE * 8, lds_max);
+  const uint32_t n_lds = std::min({V.C.n_slots, air_lds_slots(ctx), lds_fit}), n_spill = V.C.n_slots - n_lds;
   ka.code = V.d_code;
   ka.seg_off = V.d_seg_off;
   ka.n_lds = (int)n_lds;

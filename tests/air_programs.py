@@ -6,6 +6,8 @@ extension) whose constraints are written ONCE over an abstract field and interpr
 evaluated on rows in Python integers, evaluated at zeta over F_p^2. Test infrastructure only."""
 import numpy as np
 
+import oracle_lib as O
+
 P = 0xFFFFFFFF00000001
 (LOCAL, NEXT, PUBLIC, GLOBAL, CHALLENGE, CONST, ADD, SUB, MUL, NEG, INV, ASSERT_ZERO, ASSERT_ZERO_TRANSITION, ASSERT_ZERO_FIRST_ROW,
  ASSERT_ZERO_LAST_ROW, STORE) = range(16)
@@ -335,3 +337,33 @@ def lookup_programs():
 def lookup_steps(ma, mb):
     """the step list of cityprover.stark_desc / oracle_lib.stark_desc for the two map programs (as backend objects)"""
     return [("map", ma), ("cubic_inverse", 0, 3, CUBIC_MODULUS), ("map", mb), ("prefix_sum", 12, 3, True)]
+
+
+def quotient_case(prover, b, ks, db, rb, q, n_alphas, ch, seed):
+    """commit random traces, run the program on both sides, compare the committed quotient"""
+    import cityprover
+    rng = np.random.default_rng(seed)
+    n = 1 << db
+    traces = [rng.integers(0, P, (k, n), dtype=np.uint64) for k in ks]
+    pub, glo, cha = (rng.integers(0, P, k, dtype=np.uint64) for k in (b.n_public, b.n_global, b.n_challenge))
+    alphas = rng.integers(0, P, n_alphas, dtype=np.uint64)
+    G = [cityprover.PolyBatch(prover, t, rb, ch) for t in traces]
+    Ob = [O.Batch(t, rb, ch) for t in traces]
+    g, o = b.gpu(prover), b.oracle()
+    try:
+        want = O.air_quotient(o, Ob, q, alphas, pub, glo, cha)
+        Q = cityprover.air_quotient_commit(prover, g, G, q, alphas, pub, glo, cha)
+        try:
+            assert Q.k == n_alphas << q and Q.degree_bits == db and Q.rate_bits == rb and Q.cap_height == ch
+            got = Q.coeffs()
+            assert (got == want).all(), "quotient coefficients differ"
+            oq = O.Batch(want, rb, ch, True)
+            assert (Q.cap() == oq.cap()).all()
+            oq.close()
+        finally:
+            Q.close()
+        return g.info()
+    finally:
+        g.close()
+        for x in G + Ob:
+            x.close()

@@ -15,6 +15,7 @@ import pytest
 
 import air_programs as A
 import oracle_lib as O
+from air_programs import quotient_case
 
 pytestmark = pytest.mark.gpu
 P = O.P
@@ -68,36 +69,6 @@ def test_map_programs_match_oracle(prover):
     got = cityprover.air_map(prover, g, cols, publics=[5])
     g.close()
     assert (got == o.map(cols, publics=[5])).all() and got[2, 17] == 0 and (got[1] == 0).all()
-
-
-def quotient_case(prover, b, ks, db, rb, q, n_alphas, ch, seed):
-    """commit random traces, run the program on both sides, compare the committed quotient"""
-    import cityprover
-    rng = np.random.default_rng(seed)
-    n = 1 << db
-    traces = [rng.integers(0, P, (k, n), dtype=np.uint64) for k in ks]
-    pub, glo, cha = (rng.integers(0, P, k, dtype=np.uint64) for k in (b.n_public, b.n_global, b.n_challenge))
-    alphas = rng.integers(0, P, n_alphas, dtype=np.uint64)
-    G = [cityprover.PolyBatch(prover, t, rb, ch) for t in traces]
-    Ob = [O.Batch(t, rb, ch) for t in traces]
-    g, o = b.gpu(prover), b.oracle()
-    try:
-        want = O.air_quotient(o, Ob, q, alphas, pub, glo, cha)
-        Q = cityprover.air_quotient_commit(prover, g, G, q, alphas, pub, glo, cha)
-        try:
-            assert Q.k == n_alphas << q and Q.degree_bits == db and Q.rate_bits == rb and Q.cap_height == ch
-            got = Q.coeffs()
-            assert (got == want).all(), "quotient coefficients differ"
-            oq = O.Batch(want, rb, ch, True)
-            assert (Q.cap() == oq.cap()).all()
-            oq.close()
-        finally:
-            Q.close()
-        return g.info()
-    finally:
-        g.close()
-        for x in G + Ob:
-            x.close()
 
 
 @pytest.mark.parametrize("seed", range(12))
