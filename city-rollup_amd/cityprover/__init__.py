@@ -858,6 +858,105 @@ def groth16_prove(prover, pk, witness_ptr, a_ptr, b_ptr, c_ptr, r, s):
     return ((val(oa[:6]), val(oa[6:])), ((val(ob[:6]), val(ob[6:12])), (val(ob[12:18]), val(ob[18:]))), (val(oc[:6]), val(oc[6:])))
 
 
+# ---- the R1CS on the device: evaluations, satisfaction check, proof from a witness alone ----
+_u32p = ctypes.POINTER(ctypes.c_uint32)
+R1CS_NO_TERM_CLASSES = 1
+
+
+class R1csMatrix(ctypes.Structure):
+    _fields_ = [("row_ptr", _u64p), ("col", _u32p), ("coeff", _u32p)]
+
+
+class R1csDesc(ctypes.Structure):
+    _fields_ = [("n_constraints", ctypes.c_size_t), ("n_wires", ctypes.c_size_t), ("coeffs", _u64p), ("n_coeffs", ctypes.c_size_t),
+                ("a", R1csMatrix), ("b", R1csMatrix), ("c", R1csMatrix), ("flags", ctypes.c_uint)]
+
+
+class R1csInfo(ctypes.Structure):
+    _fields_ = [("n_constraints", ctypes.c_size_t), ("n_wires", ctypes.c_size_t), ("n_coeffs", ctypes.c_size_t), ("log_domain", ctypes.c_int),
+                ("nnz", ctypes.c_size_t * 3), ("longest_row", ctypes.c_size_t), ("device_bytes", ctypes.c_size_t),
+                ("long_row_threshold", ctypes.c_size_t), ("n_short_rows", ctypes.c_size_t), ("n_long_rows", ctypes.c_size_t),
+                ("n_terms_class", ctypes.c_size_t * 6)]
+
+
+ABI["cp_r1cs_bls12381_create"] = (_vp, [_vp, ctypes.POINTER(R1csDesc)])
+ABI["cp_r1cs_bls12381_destroy"] = (None, [_vp])
+ABI["cp_r1cs_bls12381_get_info"] = (ctypes.c_int, [_vp, ctypes.POINTER(R1csInfo)])
+ABI["cp_r1cs_bls12381_eval_dev"] = (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp])
+ABI["cp_r1cs_bls12381_check_dev"] = (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)])
+ABI["cp_groth16_prove_r1cs_bls12381"] = (ctypes.c_int, [_vp, ctypes.POINTER(Groth16Pk), _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p])
+
+
+def r1cs_desc(n_constraints, n_wires, coeffs, matrices, flags=0):
+    """R1csDesc over numpy arrays. coeffs: (n_coeffs, 4) uint64; matrices: three (row_ptr uint64, col uint32, coeff uint32).
+    Returns (desc, keep): `keep` holds the arrays the descriptor points into."""
+    coeffs = np.ascontiguousarray(np.asarray(coeffs, dtype=np.uint64).reshape(-1, 4))
+    d = R1csDesc()
+    d.n_constraints, d.n_wires, d.n_coeffs, d.flags = int(n_constraints), int(n_wires), coeffs.shape[0], int(flags)
+    d.coeffs = coeffs.ctypes.data_as(_u64p) if coeffs.size else None
+    keep = [coeffs]
+    for name, (row_ptr, col, coeff) in zip("abc", matrices):
+        m = getattr(d, name)
+        row_ptr = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.uint64))
+        col, coeff = (np.ascontiguousarray(np.asarray(x, dtype=np.uint32)) for x in (col, coeff))
+        m.row_ptr = row_ptr.ctypes.data_as(_u64p)
+        m.col = col.ctypes.data_as(_u32p) if col.size else None
+        m.coeff = coeff.ctypes.data_as(_u32p) if coeff.size else None
+        keep += [row_ptr, col, coeff]
+    return d, keep
+
+
+class R1cs:
+    """A constraint system resident on the device (cp_r1cs_bls12381_create)."""
+
+    def __init__(self, prover, n_constraints, n_wires, coeffs, matrices, flags=0):
+        self.prover = prover
+        desc, keep = r1cs_desc(n_constraints, n_wires, coeffs, matrices, flags)
+        self.handle = prover.lib.cp_r1cs_bls12381_create(prover.ctx, ctypes.byref(desc))
+        del keep
+        if not self.handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+        self.info = R1csInfo()
+        prover._check(prover.lib.cp_r1cs_bls12381_get_info(self.handle, ctypes.byref(self.info)))
+        self.n_pad = 1 << self.info.log_domain
+
+    def eval_dev(self, witness_ptr, a_ptr, b_ptr, c_ptr):
+        self.prover._check(self.prover.lib.cp_r1cs_bls12381_eval_dev(self.prover.ctx, self.handle, witness_ptr, a_ptr, b_ptr, c_ptr))
+
+    def eval(self, witness_ptr):
+        """A w, B w, C w as three (2^log_domain, 4) uint64 arrays"""
+        bufs = [self.prover.alloc(4 * self.n_pad) for _ in range(3)]
+        try:
+            self.eval_dev(witness_ptr, *(b.ptr for b in bufs))
+            return tuple(b.download().reshape(-1, 4) for b in bufs)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def check(self, witness_ptr):
+        """(number of violated constraints, the lowest violated one or None)"""
+        n, first = ctypes.c_size_t(), ctypes.c_size_t()
+        self.prover._check(self.prover.lib.cp_r1cs_bls12381_check_dev(self.prover.ctx, self.handle, witness_ptr, ctypes.byref(n), ctypes.byref(first)))
+        return n.value, (first.value if n.value else None)
+
+    def free(self):
+        if self.handle:
+            self.prover.lib.cp_r1cs_bls12381_destroy(self.handle)
+            self.handle = None
+
+
+def groth16_prove_r1cs(prover, pk, r1cs, witness_ptr, r, s, out=None):
+    """cp_groth16_prove_r1cs_bls12381: the proof from (key, constraint system, witness). Returns (A, B, C) as groth16_prove does.
+    out: optional (12, 24, 12)-word uint64 arrays to receive the raw coordinates (a refused call leaves them alone)."""
+    lim = lambda v: np.array([(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)], dtype=np.uint64)
+    oa, ob, oc = out if out is not None else (np.zeros(12, np.uint64), np.zeros(24, np.uint64), np.zeros(12, np.uint64))
+    rr, ss = lim(r), lim(s)
+    prover._check(prover.lib.cp_groth16_prove_r1cs_bls12381(prover.ctx, ctypes.byref(pk), r1cs.handle, witness_ptr, _ptr(rr), _ptr(ss),
+                                                            _ptr(oa), _ptr(ob), _ptr(oc)))
+    val = lambda a: sum(int(v) << (64 * j) for j, v in enumerate(a))
+    return ((val(oa[:6]), val(oa[6:])), ((val(ob[:6]), val(ob[6:12])), (val(ob[12:18]), val(ob[18:]))), (val(oc[:6]), val(oc[6:])))
+
+
 # ---- circuit files (N1) and the stored Groth16 proof form ----
 ABI["cp_circuit_load_file"] = (_vp, [_vp, ctypes.c_char_p])
 ABI["cp_circuit_save_file"] = (ctypes.c_int, [_vp, ctypes.c_char_p])

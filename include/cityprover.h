@@ -764,6 +764,66 @@ int cp_groth16_prove_bls12381(cp_ctx *ctx, const cp_groth16_pk *pk, const uint64
                               uint64_t *b_evals_dev, uint64_t *c_evals_dev, const uint64_t r[4], const uint64_t s[4],
                               uint64_t out_a[12], uint64_t out_b[24], uint64_t out_c[12]);
 
+/* ---- The R1CS on the device: from (constraint system, witness) to the evaluations and the proof ----
+ * The step in front of cp_groth16_prove_bls12381: A w, B w, C w as three sparse matrix-vector products over F_r, on the
+ * device, so that a caller hands over what a solver gives it (a constraint system once, a witness per proof) instead of
+ * computing 3 x 2^log_domain field elements on the host and uploading them.
+ * A matrix is CSR: term t of row j, row_ptr[j] <= t < row_ptr[j+1], is coeffs[coeff[t]] * w[col[t]]. The coefficient
+ * table holds the distinct coefficients (gnark's layout: a table and terms that index it). Wires are ordered as in
+ * cp_groth16_pk: public first, wire 0 the constant one, then private. A row may be empty (its value is 0) and may name a
+ * wire several times (the terms add). All arrays are host arrays and are copied; the handle lives on the context's device
+ * and may be used by any context of that device.
+ * Parity with gnark's solver output stays unpinned: the reference tree holds no constraint system and no vectors. The
+ * tests hold every evaluation against Python integers modulo r. */
+typedef struct cp_r1cs_matrix {
+  const uint64_t *row_ptr; /* n_constraints + 1 entries, row_ptr[0] = 0, non-decreasing */
+  const uint32_t *col;     /* wire of each term, < n_wires */
+  const uint32_t *coeff;   /* index of each term's coefficient, < n_coeffs */
+} cp_r1cs_matrix;
+#define CP_R1CS_NO_TERM_CLASSES 1u /* cp_r1cs_desc.flags: every term takes the general multiplication (measurement only) */
+typedef struct cp_r1cs_desc {
+  size_t n_constraints, n_wires; /* 1 <= n_constraints <= 2^28, 1 <= n_wires < 2^32 */
+  const uint64_t *coeffs;        /* n_coeffs x 4 u64, canonical (< r) */
+  size_t n_coeffs;               /* < 2^29 */
+  cp_r1cs_matrix a, b, c;
+  unsigned flags;
+} cp_r1cs_desc;
+/* What cp_r1cs_bls12381_create made of a system. Terms are sorted into classes by their coefficient, in this order:
+ * 0 (dropped), +1 (an addition), -1 (a subtraction), 2 .. 2^28 - 1 (a one-limb product), -(2 .. 2^28 - 1) (the same,
+ * subtracted), anything else (a full modular multiplication). Rows of more than long_row_threshold kept terms take a
+ * workgroup each, every other row a lane. */
+typedef struct cp_r1cs_info {
+  size_t n_constraints, n_wires, n_coeffs;
+  int log_domain;            /* the least L with 2^L >= n_constraints */
+  size_t nnz[3];             /* terms of A, B, C as given */
+  size_t longest_row;        /* terms kept (zero coefficients dropped), over the three matrices */
+  size_t device_bytes;
+  size_t long_row_threshold;
+  size_t n_short_rows, n_long_rows; /* rows per launch class, the three matrices together */
+  size_t n_terms_class[6];   /* zero, plus one, minus one, small, minus small, general */
+} cp_r1cs_info;
+typedef struct cp_r1cs_bls12381 cp_r1cs_bls12381;
+/* Validates, classifies, uploads. NULL + cp_last_error on refusal; the message names the matrix and the row. */
+cp_r1cs_bls12381 *cp_r1cs_bls12381_create(cp_ctx *ctx, const cp_r1cs_desc *desc);
+void cp_r1cs_bls12381_destroy(cp_r1cs_bls12381 *r1cs);
+int cp_r1cs_bls12381_get_info(const cp_r1cs_bls12381 *r1cs, cp_r1cs_info *out);
+/* witness_dev: n_wires x 4 u64, canonical (read, never written). Each output: 2^log_domain x 4 u64, canonical, natural
+ * order, zero from row n_constraints on: what cp_groth16_quotient_bls12381_dev and cp_groth16_prove_bls12381 read.
+ * Asynchronous on the context stream, like the other _dev entry points. */
+int cp_r1cs_bls12381_eval_dev(cp_ctx *ctx, const cp_r1cs_bls12381 *r1cs, const uint64_t *witness_dev, uint64_t *a_out_dev,
+                              uint64_t *b_out_dev, uint64_t *c_out_dev);
+/* Counts the rows j < n_constraints with (A w)_j (B w)_j != (C w)_j and reports the lowest ((size_t)-1 when there is
+ * none). Needs no output arrays; synchronises the context stream. */
+int cp_r1cs_bls12381_check_dev(cp_ctx *ctx, const cp_r1cs_bls12381 *r1cs, const uint64_t *witness_dev, size_t *n_violated_out,
+                               size_t *first_violated_out);
+/* cp_groth16_prove_bls12381 from a witness alone: refuses a key whose n_wires or log_domain differ from the system's,
+ * evaluates into buffers of its own, refuses (CP_ERR_INVALID_ARG, the message carries the first violated constraint, the
+ * outputs are not written) a witness that does not satisfy the system, then proves exactly as cp_groth16_prove_bls12381
+ * does from the same evaluations. */
+int cp_groth16_prove_r1cs_bls12381(cp_ctx *ctx, const cp_groth16_pk *pk, const cp_r1cs_bls12381 *r1cs,
+                                   const uint64_t *witness_dev, const uint64_t r[4], const uint64_t s[4], uint64_t out_a[12],
+                                   uint64_t out_b[24], uint64_t out_c[12]);
+
 
 /* The proof in the form the worker stores and the chain consumes: `CityGroth16ProofData { pi_a, pi_b_a0, pi_b_a1, pi_c }`
  * = 4 x 48 bytes (city_rollup_common/src/block_template/data.rs:6-34; produced at

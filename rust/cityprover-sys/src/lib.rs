@@ -395,6 +395,59 @@ pub fn groth16_pack_city(a_xy: &[u64; 12], b_xy: &[u64; 24], c_xy: &[u64; 12]) -
     Ok(out)
 }
 
+/// A constraint system resident on the device (`cp_r1cs_bls12381`, include/cityprover.h "The R1CS on the device"): created once
+/// from a coefficient table and three CSR matrices, then evaluated, checked or proved from per witness.
+pub struct R1cs {
+    raw: *mut ffi::CpR1csBls12381,
+}
+unsafe impl Send for R1cs {}
+unsafe impl Sync for R1cs {}
+
+impl R1cs {
+    /// `desc` points into host arrays of the caller; they are copied and may be dropped when this returns.
+    pub fn create(ctx: &Context, desc: &ffi::CpR1csDesc) -> Result<Self> {
+        let raw = unsafe { ffi::cp_r1cs_bls12381_create(ctx.raw, desc) };
+        if raw.is_null() {
+            bail!("cityprover[{}]: {}", ffi::CP_ERR_INVALID_ARG, last_error(ctx.raw));
+        }
+        Ok(Self { raw })
+    }
+
+    pub fn info(&self) -> ffi::CpR1csInfo {
+        let mut i: ffi::CpR1csInfo = unsafe { std::mem::zeroed() };
+        unsafe { ffi::cp_r1cs_bls12381_get_info(self.raw, &mut i) };
+        i
+    }
+
+    /// A w, B w, C w into three device arrays of 2^log_domain x 4 u64 (asynchronous on the context stream)
+    pub fn eval_dev(&self, ctx: &Context, witness_dev: *const u64, a_dev: *mut u64, b_dev: *mut u64, c_dev: *mut u64) -> Result<()> {
+        check(ctx.raw, unsafe { ffi::cp_r1cs_bls12381_eval_dev(ctx.raw, self.raw, witness_dev, a_dev, b_dev, c_dev) })
+    }
+
+    /// (violated constraints, the lowest violated one)
+    pub fn check_dev(&self, ctx: &Context, witness_dev: *const u64) -> Result<(usize, Option<usize>)> {
+        let (mut n, mut first) = (0usize, 0usize);
+        check(ctx.raw, unsafe { ffi::cp_r1cs_bls12381_check_dev(ctx.raw, self.raw, witness_dev, &mut n, &mut first) })?;
+        Ok((n, if n > 0 { Some(first) } else { None }))
+    }
+
+    /// The Groth16 proof (A, B, C as affine canonical coordinates) from the key, this system and a witness; an unsatisfied
+    /// witness is an error that names the first violated constraint.
+    pub fn groth16_prove(&self, ctx: &Context, pk: &ffi::CpGroth16Pk, witness_dev: *const u64, r: &[u64; 4], s: &[u64; 4]) -> Result<([u64; 12], [u64; 24], [u64; 12])> {
+        let (mut a, mut b, mut c) = ([0u64; 12], [0u64; 24], [0u64; 12]);
+        check(ctx.raw, unsafe {
+            ffi::cp_groth16_prove_r1cs_bls12381(ctx.raw, pk, self.raw, witness_dev, r.as_ptr(), s.as_ptr(), a.as_mut_ptr(), b.as_mut_ptr(), c.as_mut_ptr())
+        })?;
+        Ok((a, b, c))
+    }
+}
+
+impl Drop for R1cs {
+    fn drop(&mut self) {
+        unsafe { ffi::cp_r1cs_bls12381_destroy(self.raw) }
+    }
+}
+
 /// A straight-line AIR program compiled for the device (`cp_air_program`, include/cityprover.h "the STARK's own two steps as
 /// GENERIC device machinery"): what rust/starkyx-patch/recording_parser.rs produces by running an AIR once against a recorder.
 pub struct AirProgram {
