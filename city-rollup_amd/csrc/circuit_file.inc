@@ -20,7 +20,7 @@
 //        u32   public_input_targets[num_public_inputs][2]  (flag bit 2: row, wire of public input j in the wire matrix)
 //        u64   polynomials[num_constants + num_routed_wires][n]   constants (selectors first) then sigmas
 //   end  u64   FNV-1a 64 of every preceding byte
-// Included by cityprover.hip after prover_tail.inc.
+// Included by cityprover.hip after quotient.inc and prover_tail.inc.
 
 namespace cfile {
 

@@ -61,6 +61,39 @@ int get_prescale_table(cp_ctx *ctx, int log_n, int rate_bits, uint64_t shift, co
   return CP_OK;
 }
 
+}  // namespace
+namespace quot {  // quotient.h, included below with the proof tail
+__global__ __launch_bounds__(256) void k_fill_l0(uint64_t *out, size_t N, int log_N, int rb, const uint64_t *omega_tab, const uint64_t *zh,
+                                                 uint64_t n_field);
+}
+namespace {
+
+// L_0 on the LDE coset [N] of a shape, cached per ctx (a lane context keeps its own: tables are written on the context's stream).
+// omega_tab: power table of omega_N; zh: the caller's Z_H table (quotient.inc)
+int get_l0_table(cp_ctx *ctx, int log_n, int rate_bits, const uint64_t *omega_tab, const uint64_t *zh, const uint64_t **out) {
+  auto it = ctx->l0_tables.find({log_n, rate_bits});
+  if (it == ctx->l0_tables.end()) {
+    // filled and checked BEFORE it is cached: a failed launch (or an earlier asynchronous error surfacing here) must not
+    // leave an uninitialised table behind for every later proof of this shape (once per shape and context: the sync is free)
+    const size_t N = (size_t)1 << (log_n + rate_bits);
+    uint64_t *tab = nullptr;
+    HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&tab, N * 8));
+    int rc = [&]() -> int {
+      LAUNCH(ctx, "quotient_fill_l0", quot::k_fill_l0, dim3(blocks_for(N, 256)), dim3(256), tab, N, log_n + rate_bits, rate_bits, omega_tab, zh,
+             ((uint64_t)1 << log_n) % gl::P);
+      HIP_TRY(ctx, sync_stream(ctx));
+      return CP_OK;
+    }();
+    if (rc != CP_OK) {
+      (void)hipFree(tab);
+      return rc;
+    }
+    it = ctx->l0_tables.emplace(std::make_pair(log_n, rate_bits), tab).first;
+  }
+  *out = it->second;
+  return CP_OK;
+}
+
 // Power-on self-test of the arithmetic that is written below the compiler (gl.h: three `asm` blocks with hand-placed wait
 // states): a dozen products through every carry / borrow path and one permutation, against the same headers compiled for the
 // host (portable C paths). Run once per context; a device that disagrees never gets to prove anything.
@@ -179,7 +212,8 @@ int run_dif(cp_ctx *ctx, uint64_t *data, int log_n, size_t batch, size_t stride,
     dim3 grid((unsigned)(((size_t)1 << outer_bits) >> c), (unsigned)batch, (unsigned)ex.n_blocks);
     bool done = false;
     const bool need16 = ex.src || ex.ptab || ex.n_blocks > 1 || ex.natural_out;
-    if (L >= 4 && L + c == ntt16::LOG_TILE && (need16 || !getenv("CITYPROVER_NTT_V1"))) {
+    static const bool ntt_v1 = getenv("CITYPROVER_NTT_V1") != nullptr;  // read once per process, as CP_KNOB does
+    if (L >= 4 && L + c == ntt16::LOG_TILE && (need16 || !ntt_v1)) {
       // register radix-16 pass (ntt16.h)
       // a pass of a big transform has the GPU to itself and is occupancy-bound: half-tile exchange, five waves per SIMD; the
       // 2^12-2^15 transforms of a proof run beside other contexts' kernels: whole-tile exchange, fewer barriers (ntt16.h)
@@ -921,6 +955,7 @@ int cp_commit_dev(cp_ctx *ctx, const uint64_t *values, size_t k, int log_n, int 
 #include "transcript.h"
 #include "zs.h"
 #include "quotient.h"
+#include "quotient.inc"
 #include "prover_tail.inc"
 #include "batcher.inc"
 #include "verify.inc"

@@ -49,7 +49,7 @@ struct cp_ctx {
   struct PreKey { int log_n, rate_bits; uint64_t shift; bool operator<(const PreKey &o) const {
     return std::tie(log_n, rate_bits, shift) < std::tie(o.log_n, o.rate_bits, o.shift); } };
   std::map<PreKey, uint64_t *> prescale_tables;  // LDE pre-scale tables [2^rate_bits][n]
-  std::map<std::pair<int, int>, uint64_t *> l0_tables;  // (degree_bits, rate_bits) -> L_0 on the LDE coset [N], storage order
+  std::map<std::pair<int, int>, uint64_t *> l0_tables;  // (degree_bits, rate_bits) -> L_0 on the LDE coset [N], storage order (get_l0_table)
   std::map<std::pair<int, int>, uint64_t *> air_sel_tables;  // (degree_bits, q) -> z_last, L_0, L_(n-1) on the quotient coset [3][M] (stark.inc)
   size_t lds_per_block = 0;  // the device's shared memory per workgroup, bytes (hipDeviceAttributeMaxSharedMemoryPerBlock; asked once)
   // scratch buffer reused by natural-order NTT epilogues / merkle host paths
@@ -287,8 +287,8 @@ hipError_t sync_stream(cp_ctx *ctx) {
   return e;
 }
 
-// Launch `kernel` on the context stream; when profiling is on, bracket it with HIP events.
-#define LAUNCH(ctx, name, kernel, grid, block, ...)                                      \
+// Launch `kernel` on the context stream with `lds_bytes` of dynamic LDS; when profiling is on, bracket it with HIP events.
+#define LAUNCH_LDS(ctx, name, kernel, grid, block, lds_bytes, ...)                       \
   do {                                                                                   \
     cp_ctx::ProfRec pr__{name, nullptr, nullptr};                                        \
     if ((ctx)->profiling) {                                                              \
@@ -297,12 +297,13 @@ hipError_t sync_stream(cp_ctx *ctx) {
       pr__.e1 = prof_event(ctx);                                                         \
       (void)hipEventRecord(pr__.e0, (ctx)->stream);                                      \
     }                                                                                    \
-    hipLaunchKernelGGL(kernel, grid, block, 0, (ctx)->stream, __VA_ARGS__);              \
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (ctx)->stream, __VA_ARGS__);      \
     if ((ctx)->profiling) {                                                              \
       (void)hipEventRecord(pr__.e1, (ctx)->stream);                                      \
       (ctx)->prof_recs.push_back(pr__);                                                  \
     }                                                                                    \
     HIP_TRY(ctx, hipGetLastError());                                                     \
   } while (0)
+#define LAUNCH(ctx, name, kernel, grid, block, ...) LAUNCH_LDS(ctx, name, kernel, grid, block, 0, __VA_ARGS__)
 
 }  // namespace

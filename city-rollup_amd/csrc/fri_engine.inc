@@ -1,7 +1,7 @@
 // The FRI opening proof over ARBITRARY oracles and opening batches — plonky2 0.2.2 `PolynomialBatch::prove_openings`
 // (batch polynomial per FriBatchInfo, `fri_proof`: commit phase, proof of work, query rounds) for B independent
 // instances of one shape at once. `CircuitData::prove` is one client (four oracles, the batches at zeta and g*zeta:
-// prover_tail.inc); the C-ABI entry point cp_fri_prove (fri_prove.inc) is the other — what a STARK prover built on
+// prover_tail.inc tail_fri); the C-ABI entry point cp_fri_prove (fri_prove.inc) is the other — what a STARK prover built on
 // plonky2's FRI calls (starkyx `ByteStark::prove`: city_common_circuit/src/hash/accelerator/sha256/smartgadget.rs:518-524,
 // which proves through `plonky2::{stark::config::GenericCombinedConfig, Plonky2Air}`, smartgadget.rs:48-49).
 // Included by prover_tail.inc after its host helpers (arena, staging, ByteBuf, HostChallenger).

@@ -266,6 +266,34 @@ struct ArenaScope {
   }
 };
 
+// A7 launch on device-resident parameters: d_sig = per-proof sigma-values pointers; betas[proof*stride + c], gammas likewise
+static int zs_launch(cp_ctx *ctx, const cp_shape &sh, size_t Bn, const uint64_t *const *d_sig, const uint64_t *k_is,
+                     const uint64_t *wires, const uint64_t *betas, const uint64_t *gammas, size_t chal_stride, uint64_t *out) {
+  const int nc = sh.num_challenges, R = sh.num_routed_wires, chunk = sh.quotient_degree_factor, npp = sh.num_partial_products;
+  if (R <= 0 || (R + chunk - 1) / chunk != npp + 1 || npp + 1 > zs::MAX_CHUNKS)
+    return set_error(ctx, CP_ERR_INVALID_ARG, "num_partial_products %d inconsistent with %d routed wires in chunks of %d", npp, R, chunk);
+  const size_t n = (size_t)1 << sh.degree_bits;
+  const uint64_t *wt;
+  CP_TRY(get_pow_table(ctx, GL_ROOTS[sh.degree_bits], &wt));
+  zs::Args a;
+  a.wires = wires;
+  a.wires_proof_stride = (size_t)sh.num_wires * n;
+  a.sigmas = d_sig;
+  a.k_is = k_is;
+  a.betas = betas;
+  a.gammas = gammas;
+  a.chal_stride = chal_stride;
+  a.out = out;
+  a.out_proof_stride = (size_t)nc * (1 + npp) * n;
+  a.omega_tab = wt;
+  a.n = n;
+  a.num_routed = R; a.chunk = chunk; a.npp = npp; a.nc = nc;
+  if (a.npp + 1 <= 10) LAUNCH(ctx, "zs_chunk_products", zs::k_chunk_products<10>, dim3(blocks_for(n, 256), nc, (unsigned)Bn), dim3(256), a);
+  else LAUNCH(ctx, "zs_chunk_products", zs::k_chunk_products<zs::MAX_CHUNKS>, dim3(blocks_for(n, 256), nc, (unsigned)Bn), dim3(256), a);
+  LAUNCH(ctx, "zs_scan_rows", zs::k_scan_rows, dim3(1, nc, (unsigned)Bn), dim3(256), a);
+  return CP_OK;
+}
+
 extern "C" {
 
 void cp_free(void *p) { free(p); }
@@ -352,7 +380,6 @@ int cp_zs_partial_products_dev(cp_ctx *ctx, size_t n_proofs, cp_circuit *const *
   for (size_t i = 0; i < n_proofs * (size_t)nc; i++)
     if (betas_host[i] >= gl::P || gammas_host[i] >= gl::P) return set_error(ctx, CP_ERR_INVALID_ARG, "challenge %zu is not canonical", i);
   const size_t n = (size_t)1 << sh.degree_bits;
-  zs::Args a;
   const uint64_t **d_sig;
   uint64_t *d_bg;
   // small per-call parameter block in the arena (released by the caller's arena_reset or below)
@@ -368,24 +395,7 @@ int cp_zs_partial_products_dev(cp_ctx *ctx, size_t n_proofs, cp_circuit *const *
     CP_TRY(push(ctx, d_sig, h.data(), n_proofs * sizeof(void *)));
     CP_TRY(push(ctx, d_bg, bg.data(), bg.size() * 8));
   }
-  const uint64_t *wt;
-  CP_TRY(get_pow_table(ctx, GL_ROOTS[sh.degree_bits], &wt));
-  a.wires = wires_values_dev;
-  a.wires_proof_stride = (size_t)sh.num_wires * n;
-  a.sigmas = d_sig;
-  a.k_is = circuits[0]->k_is;
-  a.betas = d_bg;
-  a.gammas = d_bg + n_proofs * nc;
-  a.chal_stride = (size_t)nc;
-  a.out = out_dev;
-  a.out_proof_stride = (size_t)nc * (1 + npp) * n;
-  a.omega_tab = wt;
-  a.n = n;
-  a.num_routed = R; a.chunk = chunk; a.npp = npp; a.nc = nc;
-  if (a.npp + 1 <= 10) LAUNCH(ctx, "zs_chunk_products", zs::k_chunk_products<10>, dim3(blocks_for(n, 256), nc, (unsigned)n_proofs), dim3(256), a);
-  else LAUNCH(ctx, "zs_chunk_products", zs::k_chunk_products<zs::MAX_CHUNKS>, dim3(blocks_for(n, 256), nc, (unsigned)n_proofs), dim3(256), a);
-  LAUNCH(ctx, "zs_scan_rows", zs::k_scan_rows, dim3(1, nc, (unsigned)n_proofs), dim3(256), a);
-  return CP_OK;
+  return zs_launch(ctx, sh, n_proofs, d_sig, circuits[0]->k_is, wires_values_dev, d_bg, d_bg + n_proofs * nc, (size_t)nc, out_dev);
 } CP_CATCH(ctx)
 
 int cp_circuit_cs_cap(cp_circuit *c, uint64_t *cap_out) try {
@@ -394,32 +404,137 @@ int cp_circuit_cs_cap(cp_circuit *c, uint64_t *cap_out) try {
   return CP_OK;
 } CP_CATCH(c ? c->ctx : nullptr)
 
-// A7 launch on device-resident parameters: d_sig = per-proof sigma-values pointers; betas[proof*stride + c], gammas likewise
-static int zs_launch(cp_ctx *ctx, const cp_shape &sh, size_t Bn, const uint64_t *const *d_sig, const uint64_t *k_is,
-                     const uint64_t *wires, const uint64_t *betas, const uint64_t *gammas, size_t chal_stride, uint64_t *out) {
-  const int nc = sh.num_challenges, R = sh.num_routed_wires, chunk = sh.quotient_degree_factor, npp = sh.num_partial_products;
-  if (R <= 0 || (R + chunk - 1) / chunk != npp + 1 || npp + 1 > zs::MAX_CHUNKS)
-    return set_error(ctx, CP_ERR_INVALID_ARG, "num_partial_products %d inconsistent with %d routed wires in chunks of %d", npp, R, chunk);
-  const size_t n = (size_t)1 << sh.degree_bits;
-  const uint64_t *wt;
-  CP_TRY(get_pow_table(ctx, GL_ROOTS[sh.degree_bits], &wt));
-  zs::Args a;
-  a.wires = wires;
-  a.wires_proof_stride = (size_t)sh.num_wires * n;
-  a.sigmas = d_sig;
-  a.k_is = k_is;
-  a.betas = betas;
-  a.gammas = gammas;
-  a.chal_stride = chal_stride;
-  a.out = out;
-  a.out_proof_stride = (size_t)nc * (1 + npp) * n;
-  a.omega_tab = wt;
-  a.n = n;
-  a.num_routed = R; a.chunk = chunk; a.npp = npp; a.nc = nc;
-  if (a.npp + 1 <= 10) LAUNCH(ctx, "zs_chunk_products", zs::k_chunk_products<10>, dim3(blocks_for(n, 256), nc, (unsigned)Bn), dim3(256), a);
-  else LAUNCH(ctx, "zs_chunk_products", zs::k_chunk_products<zs::MAX_CHUNKS>, dim3(blocks_for(n, 256), nc, (unsigned)Bn), dim3(256), a);
-  LAUNCH(ctx, "zs_scan_rows", zs::k_scan_rows, dim3(1, nc, (unsigned)Bn), dim3(256), a);
-  return CP_OK;
+// sizes of one proof of a shape: rows, LDE points, cap digests, polynomials per oracle (constants + sigmas, wires, Z / partial
+// products, quotient chunks) and in all, opened values per proof (every polynomial at zeta, then the Z polynomials at g*zeta)
+struct TailDims {
+  size_t n, N, cap_n, k_cs, k_w, k_z, k_q, k_all, open_stride;
+  explicit TailDims(const cp_shape &sh)
+      : n((size_t)1 << sh.degree_bits), N(n << sh.rate_bits), cap_n((size_t)1 << sh.cap_height),
+        k_cs((size_t)sh.num_constants + sh.num_routed_wires), k_w(sh.num_wires), k_z((size_t)sh.num_challenges * (1 + sh.num_partial_products)),
+        k_q((size_t)sh.num_challenges * sh.quotient_degree_factor), k_all(k_cs + k_w + k_z + k_q), open_stride(k_all + sh.num_challenges) {}
+};
+// per-proof device tables of a call: oracle 0 (coeffs / lde / digests of each proof's circuit), the sigma-values table of A7, the
+// transcript head and the error flags
+struct TailTables {
+  const uint64_t **t_coeffs, **t_lde, **t_dig, **d_sig;
+  uint64_t *d_head;   // [proof][circuit_digest (4) | public_inputs_hash (4)]
+  unsigned *d_flags;
+};
+
+static int tail_setup(cp_ctx *ctx, size_t Bn, cp_circuit *const *circs, const uint64_t *const *pis, const size_t *n_pis, const TailDims &D,
+                      Transcript &T, TailTables &t) {
+  const cp_shape &sh = circs[0]->sh;
+  {
+    std::vector<const uint64_t *> h(4 * Bn);
+    for (size_t p = 0; p < Bn; p++) {
+      h[p] = circs[p]->cs.coeffs; h[Bn + p] = circs[p]->cs.lde; h[2 * Bn + p] = circs[p]->cs.digests;
+      h[3 * Bn + p] = circs[p]->cs_values + (size_t)sh.num_constants * D.n;
+    }
+    CP_TRY(arena_alloc(ctx, 4 * Bn * sizeof(void *), (void **)&t.t_coeffs));
+    t.t_lde = t.t_coeffs + Bn;
+    t.t_dig = t.t_coeffs + 2 * Bn;
+    t.d_sig = t.t_coeffs + 3 * Bn;
+    CP_TRY(push(ctx, t.t_coeffs, h.data(), 4 * Bn * sizeof(void *)));
+  }
+  // transcripts: zero state; head = circuit_digest || public_inputs_hash per proof (the hash of the public inputs is a
+  // sponge of its own over host data: computed here, it needs nothing from the device)
+  std::vector<uint64_t> head(8 * Bn);
+  CP_TRY(T.init(ctx, Bn));
+  CP_TRY(arena_alloc(ctx, Bn * 64, (void **)&t.d_head));
+  CP_TRY(arena_alloc(ctx, Bn * sizeof(unsigned), (void **)&t.d_flags));
+  HIP_TRY(ctx, hipMemsetAsync(t.d_flags, 0, Bn * sizeof(unsigned), ctx->stream));
+  host_for(Bn, [&](size_t p) {
+    uint64_t st[12] = {0};
+    for (size_t off = 0; off < n_pis[p]; off += 8) {
+      size_t c = n_pis[p] - off < 8 ? n_pis[p] - off : 8;
+      memcpy(st, pis[p] + off, c * 8);
+      poseidon::permute_host(st);
+    }
+    memcpy(&head[8 * p], circs[p]->digest, 32);
+    memcpy(&head[8 * p + 4], st, 32);  // public_inputs_hash
+  });
+  return push(ctx, t.d_head, head.data(), head.size() * 8);
+}
+
+// every polynomial of the four oracles at zeta and the Z polynomials at g*zeta: d_open [proof][open_stride], copied to `open`
+// behind the kernels; zpow = powers of the two points and (second half) of their inverses, for FRI
+static int tail_openings(cp_ctx *ctx, size_t Bn, int nc, const TailDims &D, const TailTables &t, const DevBatch *B, const gl::Ext *d_pts,
+                         gl::Ext **zpow_out, gl::Ext **d_open_out, std::vector<gl::Ext> &open) {
+  const unsigned Bu = (unsigned)Bn;
+  const size_t n = D.n;
+  gl::Ext *zpow, *d_open;
+  CP_TRY(arena_alloc(ctx, 4 * Bn * n * 16, (void **)&zpow));
+  CP_TRY(arena_alloc(ctx, Bn * D.open_stride * 16, (void **)&d_open));
+  LAUNCH(ctx, "fri_ext_powers", fri::k_ext_powers, dim3(blocks_for(n, 256), 4 * Bu), dim3(256), d_pts, n, zpow);
+  size_t o = 0;
+  LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)D.k_cs, Bu), dim3(256), (const uint64_t *)nullptr,
+         (size_t)0, t.t_coeffs, n, zpow, 2 * n, d_open, D.open_stride, o);
+  o += D.k_cs;
+  for (int b = 1; b < 4; b++) {
+    LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)B[b].k, Bu), dim3(256), B[b].coeffs,
+           B[b].coeffs_stride, (const uint64_t *const *)nullptr, n, zpow, 2 * n, d_open, D.open_stride, o);
+    o += B[b].k;
+  }
+  LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)nc, Bu), dim3(256), B[2].coeffs, B[2].coeffs_stride,
+         (const uint64_t *const *)nullptr, n, zpow + n, 2 * n, d_open, D.open_stride, o);
+  open.resize(Bn * D.open_stride);
+  *zpow_out = zpow;
+  *d_open_out = d_open;
+  return fetch_async(ctx, open.data(), d_open, open.size() * 16);
+}
+
+// the FRI opening proof: PolynomialBatch::prove_openings over the four oracles, batches at zeta and g*zeta
+static int tail_fri(cp_ctx *ctx, size_t Bn, const cp_shape &sh, const TailDims &D, const TailTables &t, const DevBatch *B, const gl::Ext *zpow,
+                    const gl::Ext *d_open, Transcript &T, const int *use_pow, const uint64_t *pow_ov, FriHostOut &fri_out) {
+  const int nc = sh.num_challenges;
+  std::vector<OracleRef> oracles(4);
+  oracles[0].k = D.k_cs;
+  oracles[0].t_coeffs = t.t_coeffs; oracles[0].t_lde = t.t_lde; oracles[0].t_dig = t.t_dig;
+  for (int b = 1; b < 4; b++) {
+    OracleRef &O = oracles[b];
+    O.k = B[b].k;
+    O.coeffs = B[b].coeffs; O.lde = B[b].lde; O.digests = B[b].digests;
+    O.coeffs_stride = B[b].coeffs_stride; O.lde_stride = B[b].lde_stride; O.dig_stride = B[b].dig_stride;
+    O.salt = B[b].salt; O.salt_stride = B[b].salt_stride; O.n_salt = B[b].n_salt;
+  }
+  std::vector<FriBatchDesc> fbatches(2);  // plonky2 `FRI_ORACLES` / `fri_instance`: everything at zeta, the Z polynomials at g*zeta
+  fbatches[0].ranges = {{0, 0, (uint32_t)D.k_cs}, {1, 0, (uint32_t)D.k_w}, {2, 0, (uint32_t)D.k_z}, {3, 0, (uint32_t)D.k_q}};
+  fbatches[0].n_polys = D.k_all;
+  fbatches[1].ranges = {{2, 0, (uint32_t)nc}};
+  fbatches[1].n_polys = (size_t)nc;
+  FriCfg cfg;
+  cfg.rate_bits = sh.rate_bits; cfg.cap_height = sh.cap_height; cfg.pow_bits = sh.pow_bits; cfg.num_query_rounds = sh.num_query_rounds;
+  cfg.n_arity = sh.n_arity;
+  for (int l = 0; l < 8; l++) cfg.arity_bits[l] = sh.arity_bits[l];
+  // observe_openings: the zeta batch, then zs_next — exactly the layout of d_open
+  const tr::Seg opened{(const uint64_t *)d_open, nullptr, D.open_stride * 2, (uint32_t)(D.open_stride * 2)};
+  return fri_prove_impl(ctx, Bn, sh.degree_bits, cfg, oracles, fbatches, zpow, zpow + 2 * Bn * D.n, T, opened, use_pow, pow_ov, t.d_flags, fri_out);
+}
+
+// bincode ProofWithPublicInputs of every proof
+static void tail_encode(size_t Bn, const cp_shape &sh, const TailDims &D, const DevBatch *B, const std::vector<gl::Ext> &open,
+                        const FriHostOut &fri_out, const uint64_t *const *pis, const size_t *n_pis, std::vector<ByteBuf> &outs) {
+  const size_t nc = sh.num_challenges;
+  outs.resize(Bn);
+  for (size_t p = 0; p < Bn; p++) {
+    ByteBuf &out = outs[p];
+    out.v.reserve(8 * ((size_t)sh.num_query_rounds * fri_out.words + 8192 + n_pis[p]));
+    for (int b = 1; b <= 3; b++) { out.u64(D.cap_n); out.felts(B[b].cap_host.data() + p * D.cap_n * 4, D.cap_n * 4); }
+    const uint64_t *o = (const uint64_t *)(open.data() + p * D.open_stride);
+    size_t pos = 0;
+    auto put = [&](size_t cnt, size_t at) { out.u64(cnt); out.felts(o + 2 * at, 2 * cnt); };
+    put(sh.num_constants, pos); pos += sh.num_constants;
+    put(sh.num_routed_wires, pos); pos += sh.num_routed_wires;
+    put(D.k_w, pos); pos += D.k_w;
+    put(nc, pos);                 // plonk_zs
+    put(nc, D.k_all);             // plonk_zs_next
+    put(D.k_z - nc, pos + nc);    // partial_products
+    pos += D.k_z;
+    put(D.k_q, pos);
+    out.u64(0); out.u64(0);       // lookup_zs, lookup_zs_next
+    fri_out.bytes(p, out);        // FriProof
+    out.u64(n_pis[p]); out.felts(pis[p], n_pis[p]);
+  }
 }
 
 // `full`: wires -> proof (Z / partial products and the quotient chunks are computed here, A7 + A8);
@@ -436,409 +551,83 @@ static int prove_tail_batch_impl(cp_ctx *ctx, size_t Bn, cp_circuit *const *circ
   if ((circs[0]->sh.zero_knowledge != 0) != (salts_dev != nullptr))
     return set_error(ctx, CP_ERR_INVALID_ARG, circs[0]->sh.zero_knowledge ? "zero-knowledge circuit: use the *_zk entry point (salts needed)"
                                                                           : "salts given for a circuit that is not zero-knowledge");
-  const cp_shape &sh = circs[0]->sh;
+  const cp_circuit &c0 = *circs[0];
+  const cp_shape &sh = c0.sh;
   const int db = sh.degree_bits, rb = sh.rate_bits, ch = sh.cap_height, nc = sh.num_challenges;
-  const size_t n = (size_t)1 << db, N = n << rb, cap_n = (size_t)1 << ch;
-  const size_t k_cs = (size_t)sh.num_constants + sh.num_routed_wires, k_w = sh.num_wires,
-               k_z = (size_t)nc * (1 + sh.num_partial_products), k_q = (size_t)nc * sh.quotient_degree_factor;
-  const size_t k_all = k_cs + k_w + k_z + k_q;
-  const unsigned Bu = (unsigned)Bn;
-  auto dalloc = [&](size_t bytes, void **p) -> int { return arena_alloc(ctx, bytes, p); };
-
-  // oracle 0 pointer tables (coeffs / lde / digests of each proof's circuit), the sigma-values table of A7
-  const uint64_t **t_coeffs, **t_lde, **t_dig, **d_sig;
-  {
-    std::vector<const uint64_t *> h(4 * Bn);
-    for (size_t p = 0; p < Bn; p++) {
-      h[p] = circs[p]->cs.coeffs; h[Bn + p] = circs[p]->cs.lde; h[2 * Bn + p] = circs[p]->cs.digests;
-      h[3 * Bn + p] = circs[p]->cs_values + (size_t)sh.num_constants * n;
-    }
-    CP_TRY(dalloc(4 * Bn * sizeof(void *), (void **)&t_coeffs));
-    t_lde = t_coeffs + Bn;
-    t_dig = t_coeffs + 2 * Bn;
-    d_sig = t_coeffs + 3 * Bn;
-    CP_TRY(push(ctx, t_coeffs, h.data(), 4 * Bn * sizeof(void *)));
-  }
-  // transcripts: zero state; head = circuit_digest || public_inputs_hash per proof (the hash of the public inputs is a
-  // sponge of its own over host data: computed here, it needs nothing from the device)
+  const TailDims D(sh);
+  const size_t n = D.n, N = D.N;
   Transcript T;
-  uint64_t *d_head;
-  unsigned *d_flags;
-  std::vector<uint64_t> head(8 * Bn);
-  CP_TRY(T.init(ctx, Bn));
-  CP_TRY(dalloc(Bn * 64, (void **)&d_head));
-  CP_TRY(dalloc(Bn * sizeof(unsigned), (void **)&d_flags));
-  HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, Bn * sizeof(unsigned), ctx->stream));
-  host_for(Bn, [&](size_t p) {
-    uint64_t st[12] = {0};
-    for (size_t off = 0; off < n_pis[p]; off += 8) {
-      size_t c = n_pis[p] - off < 8 ? n_pis[p] - off : 8;
-      memcpy(st, pis[p] + off, c * 8);
-      poseidon::permute_host(st);
-    }
-    memcpy(&head[8 * p], circs[p]->digest, 32);
-    memcpy(&head[8 * p + 4], st, 32);  // public_inputs_hash
-  });
-  CP_TRY(push(ctx, d_head, head.data(), head.size() * 8));
+  TailTables t;
+  CP_TRY(tail_setup(ctx, Bn, circs, pis, n_pis, D, T, t));
 
   host_phase(ctx, "commit");
   // ---- commitments + transcript head -----------------------------------------------------------
   DevBatch B[4];
-  B[0].k = k_cs;
-  CP_TRY(batch_alloc(ctx, B[1], Bn, k_w, n, N, ch));
+  B[0].k = D.k_cs;
   if (salts_dev)
     for (int b = 1; b <= 3; b++) {
       B[b].salt = salts_dev + (size_t)(b - 1) * CP_SALT_SIZE * N;
       B[b].salt_stride = (size_t)3 * CP_SALT_SIZE * N;
       B[b].n_salt = CP_SALT_SIZE;
     }
-  CP_TRY(cp_commit_batch_dev(ctx, wires_values, k_w, Bn, db, rb, ch, B[1].coeffs, B[1].lde, B[1].digests, B[1].cap));
-  if (B[1].salt)  // the leaves are longer than what the plain commitment hashed: rebuild the trees over values + salt
-    CP_TRY(merkle_cols_batch(ctx, B[1].lde, N, k_w, N, Bn, k_w * N, ch, B[1].digests, B[1].cap, B[1].salt, B[1].n_salt, B[1].salt_stride));
-  auto cap_seg = [&](const DevBatch &b) { return tr::Seg{b.cap, nullptr, cap_n * 4, (uint32_t)(cap_n * 4)}; };
-  auto fetch_caps = [&](DevBatch &b) -> int {
-    b.cap_host.resize(Bn * cap_n * 4);
-    return fetch_async(ctx, b.cap_host.data(), b.cap, b.cap_host.size() * 8);
+  // oracle b: k polynomials per proof, given as values over <omega_n> or (values == nullptr) as coefficients; its caps are copied back
+  auto commit = [&](int b, size_t k, const uint64_t *values, const uint64_t *coeffs) -> int {
+    DevBatch &O = B[b];
+    CP_TRY(batch_alloc(ctx, O, Bn, k, n, N, ch));
+    if (values) {
+      CP_TRY(cp_commit_batch_dev(ctx, values, k, Bn, db, rb, ch, O.coeffs, O.lde, O.digests, O.cap));
+    } else {  // LDE only
+      CP_TRY(cp_d2d(ctx, O.coeffs, coeffs, Bn * k * n * 8));
+      CP_TRY(cp_lde_dev(ctx, O.coeffs, n, db, rb, Bn * k, 7, CP_NTT_BITREV_OUT, O.lde, N));
+    }
+    if (!values || O.salt)  // no trees yet, or the leaves are longer than what the plain commitment hashed: trees over values + salt
+      CP_TRY(merkle_cols_batch(ctx, O.lde, N, k, N, Bn, k * N, ch, O.digests, O.cap, O.salt, O.n_salt, O.salt_stride));
+    O.cap_host.resize(Bn * D.cap_n * 4);
+    return fetch_async(ctx, O.cap_host.data(), O.cap, O.cap_host.size() * 8);
   };
-  CP_TRY(fetch_caps(B[1]));
+  auto cap_seg = [&](const DevBatch &b) { return tr::Seg{b.cap, nullptr, D.cap_n * 4, (uint32_t)(D.cap_n * 4)}; };
+  CP_TRY(commit(1, D.k_w, wires_values, nullptr));
   uint64_t *d_chal;  // [proof][betas (nc) | gammas (nc)]: what the quotient kernels read; A7 reads it with stride 2 nc
-  CP_TRY(dalloc(Bn * 2 * nc * 8, (void **)&d_chal));
-  CP_TRY(transcript_step(ctx, T, {tr::Seg{d_head, nullptr, 8, 8}, cap_seg(B[1])}, 2 * nc, d_chal, (size_t)2 * nc));
+  CP_TRY(arena_alloc(ctx, Bn * 2 * nc * 8, (void **)&d_chal));
+  CP_TRY(transcript_step(ctx, T, {tr::Seg{t.d_head, nullptr, 8, 8}, cap_seg(B[1])}, 2 * nc, d_chal, (size_t)2 * nc));
   if (full) {  // A7: Z and partial products from the witness and (beta, gamma)
     uint64_t *zs_vals;
-    CP_TRY(dalloc(Bn * k_z * n * 8, (void **)&zs_vals));
-    CP_TRY(zs_launch(ctx, sh, Bn, d_sig, circs[0]->k_is, wires_values, d_chal, d_chal + nc, (size_t)2 * nc, zs_vals));
+    CP_TRY(arena_alloc(ctx, Bn * D.k_z * n * 8, (void **)&zs_vals));
+    CP_TRY(zs_launch(ctx, sh, Bn, t.d_sig, c0.k_is, wires_values, d_chal, d_chal + nc, (size_t)2 * nc, zs_vals));
     zs_pp_values = zs_vals;
   }
-  CP_TRY(batch_alloc(ctx, B[2], Bn, k_z, n, N, ch));
-  CP_TRY(cp_commit_batch_dev(ctx, zs_pp_values, k_z, Bn, db, rb, ch, B[2].coeffs, B[2].lde, B[2].digests, B[2].cap));
-  if (B[2].salt)
-    CP_TRY(merkle_cols_batch(ctx, B[2].lde, N, k_z, N, Bn, k_z * N, ch, B[2].digests, B[2].cap, B[2].salt, B[2].n_salt, B[2].salt_stride));
-  CP_TRY(fetch_caps(B[2]));
+  CP_TRY(commit(2, D.k_z, zs_pp_values, nullptr));
   uint64_t *d_alphas;  // [proof][nc]
-  CP_TRY(dalloc(Bn * nc * 8, (void **)&d_alphas));
+  CP_TRY(arena_alloc(ctx, Bn * nc * 8, (void **)&d_alphas));
   CP_TRY(transcript_step(ctx, T, {cap_seg(B[2])}, nc, d_alphas, (size_t)nc));
   if (full) {  // A8: quotient values on the LDE coset -> coefficients -> degree-n chunks
-    const cp_circuit &c0 = *circs[0];
-    if (nc > quot::MAXC) return set_error(ctx, CP_ERR_UNSUPPORTED, "more than %d challenges", quot::MAXC);
-    if ((1 << rb) != sh.quotient_degree_factor)
-      return set_error(ctx, CP_ERR_UNSUPPORTED, "quotient_degree_factor must equal 2^rate_bits");
-    quot::Args a;
-    memset(&a, 0, sizeof a);
-    int ngc = 0;
-    for (size_t gi = 0; gi < c0.gates.size(); gi++) {
-      a.gates[gi] = c0.gates[gi];
-      int k = quot::gate_num_constraints(c0.gates[gi]);
-      if (k > ngc) ngc = k;
-    }
-    a.n_gates = (int)c0.gates.size();
-    a.num_selectors = c0.num_selectors;
-    a.n_terms = nc + nc * (sh.num_partial_products + 1) + ngc;
-    // small tables: alpha powers (on the device, from the challenges), Z_H on the coset and its inverses (shape constants)
-    std::vector<uint64_t> zh(2u << rb);
-    const uint64_t gpn = gl::pow(7, n), w8 = GL_ROOTS[rb];
-    for (int i = 0; i < (1 << rb); i++) {
-      zh[i] = gl::sub(gl::mul(gpn, gl::pow(w8, i)), 1);
-      zh[(1 << rb) + i] = gl::inv(zh[i]);
-    }
-    uint64_t *d_ap, *d_zh, *qv;
-    CP_TRY(dalloc(Bn * nc * (size_t)a.n_terms * 8, (void **)&d_ap));
-    CP_TRY(dalloc(zh.size() * 8, (void **)&d_zh));
-    CP_TRY(dalloc(Bn * nc * N * 8, (void **)&qv));
-    LAUNCH(ctx, "quotient_alpha_powers", tr::k_alpha_powers, dim3(blocks_for((size_t)a.n_terms, 64), Bu * (unsigned)nc), dim3(64), d_alphas, a.n_terms, d_ap);
-    CP_TRY(push(ctx, d_zh, zh.data(), zh.size() * 8));
-    const uint64_t *wtN;
-    CP_TRY(get_pow_table(ctx, GL_ROOTS[db + rb], &wtN));
-    a.cs_lde = t_lde;
-    a.wires_lde = B[1].lde; a.wires_stride = B[1].lde_stride;
-    a.zs_lde = B[2].lde; a.zs_stride = B[2].lde_stride;
-    a.k_is = c0.k_is;
-    a.chal = d_chal;  // [proof][2][nc]
-    a.apow = d_ap;
-    a.pi_hash = d_head + 4;  // [proof] at stride 8: see pi_stride
-    a.pi_stride = 8;
-    a.zh = d_zh; a.zh_inv = d_zh + (1 << rb);
-    a.omega_tab = wtN;
-    {  // L_0 table of this shape (a lane context keeps its own: tables are written on the context's stream)
-      auto it = ctx->l0_tables.find({db, rb});
-      if (it == ctx->l0_tables.end()) {
-        // filled and checked BEFORE it is cached: a failed launch (or an earlier asynchronous error surfacing here) must not
-        // leave an uninitialised table behind for every later proof of this shape (once per shape and context: the sync is free)
-        uint64_t *tab = nullptr;
-        HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&tab, N * 8));
-        int frc = [&]() -> int {
-          LAUNCH(ctx, "quotient_fill_l0", quot::k_fill_l0, dim3(blocks_for(N, 256)), dim3(256), tab, N, db + rb, rb, wtN, d_zh,
-                 (uint64_t)n % gl::P);
-          HIP_TRY(ctx, sync_stream(ctx));
-          return CP_OK;
-        }();
-        if (frc != CP_OK) {
-          (void)hipFree(tab);
-          return frc;
-        }
-        it = ctx->l0_tables.emplace(std::make_pair(db, rb), tab).first;
-      }
-      a.l0_tab = it->second;
-    }
-    a.out = qv; a.out_stride = (size_t)nc * N;
-    a.n_field = (uint64_t)n % gl::P;
-    a.N = N; a.log_N = db + rb; a.rb = rb;
-    a.ncst = sh.num_constants; a.R = sh.num_routed_wires; a.W = sh.num_wires; a.nc = nc; a.npp = sh.num_partial_products;
-    a.chunk = sh.quotient_degree_factor;
-    const dim3 qgrid(blocks_for(N, 256), Bu), qblock(256);
-    const int quot_flip = (int)CP_KNOB(ctx, "QUOT_FLIP", 1);
-    a.flip = quot_flip;
-    const int t0 = nc + nc * (sh.num_partial_products + 1);
-    a.t0_gates = t0;
-    a.parts = nullptr;
-    a.n_parts = 0;
-    a.acc = nullptr;
-    // up to four proofs cannot fill the chip with a launch per gate: every piece of the quotient as a slice of ONE grid
-    // (quotient.h k_quot_all; CITYPROVER_QUOT_ALL_MAX = largest batch that takes this form, 0 = never)
-    const size_t quot_all_max = (size_t)CP_KNOB(ctx, "QUOT_ALL_MAX", 4);
-    const bool quot_all = Bn <= quot_all_max;
-    // CITYPROVER_QUOT_TILE=1: the whole quotient of a 64-point tile in one workgroup, wires staged in LDS once, one wave per piece
-    // (quotient.h k_quot_tile). It reads every wire column ONCE - and it is OFF by default because it measured 20 % slower end to
-    // end (profiles/r04_quot_tile_ab.jsonl: 2 075-2 091 -> 1 659-1 675 proofs/s at 64 blocks in flight, one block alone 58.6 -> 61.4-62.1 ms):
-    // a workgroup is twelve to sixteen waves of DIFFERENT lengths on one CU, three or four per SIMD at 126 registers, and ends
-    // with its PoseidonGate wave, which then runs nearly alone - where a launch per gate keeps eight like waves on every SIMD.
-    // The quotient is bound by the latency of its chains, not by HBM (the proof moves 0.5 GB at 1.1 TB/s): trading traffic for
-    // occupancy was the wrong trade. Kept for the record and for shapes where it could pay (bytes equal: the GPU suite ran on it).
-    const int quot_tile = (int)CP_KNOB(ctx, "QUOT_TILE", 0);
-    bool tiled = false;
-    if (!quot_all && quot_tile && N % quot::TILE == 0) {
-      // pieces and what they cost (M VALU instructions per proof at the product shape, profiles/r04_pmc_qbench.json: only the
-      // proportions matter)
-      struct Piece { int kind, gi; double w; };
-      std::vector<Piece> pieces{{0, -1, 7.1}};
-      quot::ArithGroup G{-1, -1, -1, -1, -1};
-      int members = 0;
-      bool in_group[quot::MAX_GATES] = {false};
-      for (int gi = 0; gi < a.n_gates; gi++) {
-        int *slot = nullptr;
-        switch (a.gates[gi].type) {
-          case gates::CONSTANT: slot = &G.constant; break;
-          case gates::PUBLIC_INPUT: slot = &G.public_input; break;
-          case gates::ARITHMETIC: slot = &G.arithmetic; break;
-          case gates::ARITHMETIC_EXT: slot = &G.arithmetic_ext; break;
-          case gates::MUL_EXT: slot = &G.mul_ext; break;
-          default: break;
-        }
-        if (slot && *slot < 0) { *slot = gi; in_group[gi] = true; members++; }
-      }
-      if (members < 2) {
-        for (int gi = 0; gi < a.n_gates; gi++) in_group[gi] = false;
-        G = quot::ArithGroup{-1, -1, -1, -1, -1};
-      } else pieces.push_back({2, -1, 4.5});
-      for (int gi = 0; gi < a.n_gates; gi++) {
-        if (in_group[gi] || a.gates[gi].type == gates::NOOP) continue;
-        double w = 3.0;
-        switch (a.gates[gi].type) {
-          case gates::POSEIDON: w = 9.7; break;
-          case gates::REDUCING: w = 4.5; break;
-          case gates::COMPARISON: w = 4.2; break;
-          case gates::REDUCING_EXT: w = 3.5; break;
-          case gates::COSET_INTERPOLATION: w = 3.2; break;
-          case gates::BASE_SUM: w = 2.9; break;
-          case gates::RANDOM_ACCESS: w = 1.8; break;
-          case gates::POSEIDON_MDS: w = 1.1; break;
-          case gates::ARITHMETIC: case gates::ARITHMETIC_EXT: case gates::MUL_EXT: w = 1.5; break;
-          case gates::CONSTANT: case gates::PUBLIC_INPUT: w = 0.2; break;
-          default: break;
-        }
-        pieces.push_back({1, gi, w});
-      }
-      // longest piece first onto the lightest of four bins; wave w of a workgroup runs on SIMD w mod 4, so slot w takes from bin w mod 4
-      std::stable_sort(pieces.begin(), pieces.end(), [](const Piece &x, const Piece &y) { return x.w > y.w; });
-      std::vector<Piece> bins[4];
-      double load[4] = {0, 0, 0, 0};
-      for (const Piece &pc : pieces) {
-        int b = 0;
-        for (int k = 1; k < 4; k++)
-          if (load[k] < load[b]) b = k;
-        bins[b].push_back(pc);
-        load[b] += pc.w;
-      }
-      size_t depth = 0;
-      for (auto &b : bins) depth = std::max(depth, b.size());
-      const size_t lds = std::max((size_t)a.W, 4 * depth * quot::MAXC) * quot::TILE * 8;
-      if (depth >= 1 && depth <= 4 && lds <= 160 * 1024) {
-        quot::TilePieces P{};
-        P.n = (int)(4 * depth);
-        P.G = G;
-        for (size_t d = 0; d < depth; d++)
-          for (int b = 0; b < 4; b++) {
-            const size_t slot = 4 * d + b;
-            if (d < bins[b].size()) { P.kind[slot] = bins[b][d].kind; P.gi[slot] = bins[b][d].gi; }
-            else { P.kind[slot] = 1; P.gi[slot] = -1; }  // an empty slot: a "gate" without constraints
-          }
-        if (lds > 64 * 1024)  // per device: asked for whenever it is needed (a host-side table lookup)
-          HIP_TRY(ctx, hipFuncSetAttribute((const void *)quot::k_quot_tile, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        cp_ctx::ProfRec pr{"quotient_tile", nullptr, nullptr};
-        if (ctx->profiling) {
-          pr.e0 = prof_event(ctx);
-          pr.e1 = prof_event(ctx);
-          (void)hipEventRecord(pr.e0, ctx->stream);
-        }
-        hipLaunchKernelGGL(quot::k_quot_tile, dim3((unsigned)(N / quot::TILE), Bu), dim3((unsigned)(P.n * quot::TILE)), lds, ctx->stream, a, P);
-        if (ctx->profiling) {
-          (void)hipEventRecord(pr.e1, ctx->stream);
-          ctx->prof_recs.push_back(pr);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        tiled = true;
-      }
-    }
-    if (tiled) {
-      // nothing else to launch: the tile kernel divides by Z_H and writes the natural order itself
-    } else if (quot_all) {
-      a.n_parts = a.n_gates + 1;
-      CP_TRY(dalloc((size_t)a.n_parts * Bn * nc * N * 8, (void **)&a.parts));
-      LAUNCH(ctx, "quotient_all", quot::k_quot_all, dim3(blocks_for(N, 256), Bu, (unsigned)a.n_parts), qblock, a);
-    } else {
-      CP_TRY(dalloc(Bn * nc * N * 8, (void **)&a.acc));
-      LAUNCH(ctx, "quotient_perm", quot::k_quot_perm, qgrid, qblock, a);
-    }
-    // gates that read the same first wires of a row as ONE launch (quotient.h k_quot_arith_group; CITYPROVER_QUOT_GROUP=0: a launch each)
-    const int quot_group = (int)CP_KNOB(ctx, "QUOT_GROUP", 1);
-    bool grouped[quot::MAX_GATES] = {false};
-    if (!quot_all && !tiled && quot_group) {
-      quot::ArithGroup G{-1, -1, -1, -1, -1};
-      int members = 0;
-      for (int gi = 0; gi < a.n_gates; gi++) {
-        int *slot = nullptr;
-        switch (a.gates[gi].type) {
-          case gates::CONSTANT: slot = &G.constant; break;
-          case gates::PUBLIC_INPUT: slot = &G.public_input; break;
-          case gates::ARITHMETIC: slot = &G.arithmetic; break;
-          case gates::ARITHMETIC_EXT: slot = &G.arithmetic_ext; break;
-          case gates::MUL_EXT: slot = &G.mul_ext; break;
-          default: break;
-        }
-        if (slot && *slot < 0) {  // a second gate of a type (same type, other parameters) keeps its own launch
-          *slot = gi;
-          grouped[gi] = true;
-          members++;
-        }
-      }
-      if (members >= 2) {
-        if (nc <= 2) LAUNCH(ctx, "quotient_arith_group", quot::k_quot_arith_group<2>, qgrid, qblock, a, G, t0);
-        else LAUNCH(ctx, "quotient_arith_group", quot::k_quot_arith_group<quot::MAXC>, qgrid, qblock, a, G, t0);
-      } else {
-        for (int gi = 0; gi < a.n_gates; gi++) grouped[gi] = false;
-      }
-    }
-    for (int gi = 0; gi < a.n_gates && !quot_all && !tiled; gi++) {
-      if (grouped[gi]) continue;
-      switch (a.gates[gi].type) {
-#define CITY_QUOT_GATE(T, NAME) \
-  case gates::T: LAUNCH(ctx, "quotient_" NAME, quot::k_quot_gate<gates::T>, qgrid, qblock, a, gi, t0); break;
-        CITY_QUOT_GATE(CONSTANT, "constant") CITY_QUOT_GATE(PUBLIC_INPUT, "public_input") CITY_QUOT_GATE(ARITHMETIC, "arithmetic")
-        CITY_QUOT_GATE(POSEIDON, "poseidon") CITY_QUOT_GATE(COMPARISON, "comparison") CITY_QUOT_GATE(U32_ARITHMETIC, "u32_arithmetic")
-        CITY_QUOT_GATE(U32_RANGE_CHECK, "u32_range_check") CITY_QUOT_GATE(U32_ADD_MANY, "u32_add_many")
-        CITY_QUOT_GATE(U32_SUBTRACTION, "u32_subtraction") CITY_QUOT_GATE(U32_INTERLEAVE, "u32_interleave")
-        CITY_QUOT_GATE(UNINTERLEAVE_TO_U32, "uninterleave_to_u32") CITY_QUOT_GATE(UNINTERLEAVE_TO_B32, "uninterleave_to_b32")
-        CITY_QUOT_GATE(ARITHMETIC_EXT, "arithmetic_ext") CITY_QUOT_GATE(MUL_EXT, "mul_ext") CITY_QUOT_GATE(BASE_SUM, "base_sum")
-        CITY_QUOT_GATE(RANDOM_ACCESS, "random_access") CITY_QUOT_GATE(REDUCING, "reducing") CITY_QUOT_GATE(REDUCING_EXT, "reducing_ext")
-        CITY_QUOT_GATE(POSEIDON_MDS, "poseidon_mds") CITY_QUOT_GATE(COSET_INTERPOLATION, "coset_interpolation")
-        CITY_QUOT_GATE(EXPONENTIATION, "exponentiation")
-#undef CITY_QUOT_GATE
-        default: break;  // Noop: no constraints
-      }
-    }
-    if (!tiled) LAUNCH(ctx, "quotient_finish", quot::k_quot_finish, qgrid, qblock, a);
-    // coset iFFT (natural in, natural out): coefficients; chunk j of challenge c = qv[c][j*n .. (j+1)*n)
-    CP_TRY(cp_ntt_dev(ctx, qv, db + rb, Bn * nc, N, CP_NTT_INVERSE | CP_NTT_COSET, 7));
+    uint64_t *qv;
+    CP_TRY(quot_launch(ctx, sh, Bn, c0.gates, c0.num_selectors, c0.k_is, t.t_lde, B[1].lde, B[1].lde_stride, B[2].lde, B[2].lde_stride, d_chal,
+                       d_alphas, t.d_head, &qv));
     quotient_coeffs = qv;
   }
-  // quotient chunks in coefficient form: LDE + trees only
-  CP_TRY(batch_alloc(ctx, B[3], Bn, k_q, n, N, ch));
-  CP_TRY(cp_d2d(ctx, B[3].coeffs, quotient_coeffs, Bn * k_q * n * 8));
-  CP_TRY(cp_lde_dev(ctx, B[3].coeffs, n, db, rb, Bn * k_q, 7, CP_NTT_BITREV_OUT, B[3].lde, N));
-  CP_TRY(merkle_cols_batch(ctx, B[3].lde, N, k_q, N, Bn, k_q * N, ch, B[3].digests, B[3].cap, B[3].salt, B[3].n_salt, B[3].salt_stride));
-  CP_TRY(fetch_caps(B[3]));
+  CP_TRY(commit(3, D.k_q, nullptr, quotient_coeffs));  // quotient chunks in coefficient form
   // zeta, and from it the two opening points [proof][zeta, g*zeta] and their inverses (plonky2: zeta must not lie in the subgroup)
   uint64_t *d_zeta;
   gl::Ext *d_pts;
-  CP_TRY(dalloc(Bn * 16, (void **)&d_zeta));
-  CP_TRY(dalloc(4 * Bn * 16, (void **)&d_pts));
+  CP_TRY(arena_alloc(ctx, Bn * 16, (void **)&d_zeta));
+  CP_TRY(arena_alloc(ctx, 4 * Bn * 16, (void **)&d_pts));
   CP_TRY(transcript_step(ctx, T, {cap_seg(B[3])}, 2, d_zeta, 2));
-  LAUNCH(ctx, "plonk_points", tr::k_plonk_points, dim3(blocks_for(Bn, 64)), dim3(64), d_zeta, Bu, GL_ROOTS[db], db, d_pts, d_flags);
+  LAUNCH(ctx, "plonk_points", tr::k_plonk_points, dim3(blocks_for(Bn, 64)), dim3(64), d_zeta, (unsigned)Bn, GL_ROOTS[db], db, d_pts, t.d_flags);
 
   host_phase(ctx, "openings");
-  // ---- openings ---------------------------------------------------------------------------------
   gl::Ext *zpow, *d_open;
-  CP_TRY(dalloc(4 * Bn * n * 16, (void **)&zpow));
-  gl::Ext *zinv = zpow + 2 * Bn * n;
-  const size_t open_stride = k_all + nc;
-  CP_TRY(dalloc(Bn * open_stride * 16, (void **)&d_open));
-  LAUNCH(ctx, "fri_ext_powers", fri::k_ext_powers, dim3(blocks_for(n, 256), 4 * Bu), dim3(256), d_pts, n, zpow);
-  {
-    size_t o = 0;
-    LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)k_cs, Bu), dim3(256), (const uint64_t *)nullptr,
-           (size_t)0, t_coeffs, n, zpow, 2 * n, d_open, open_stride, o);
-    o += k_cs;
-    for (int b = 1; b < 4; b++) {
-      LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)B[b].k, Bu), dim3(256), B[b].coeffs,
-             B[b].coeffs_stride, (const uint64_t *const *)nullptr, n, zpow, 2 * n, d_open, open_stride, o);
-      o += B[b].k;
-    }
-    LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)nc, Bu), dim3(256), B[2].coeffs, B[2].coeffs_stride,
-           (const uint64_t *const *)nullptr, n, zpow + n, 2 * n, d_open, open_stride, o);
-  }
-  std::vector<gl::Ext> open(Bn * open_stride);
-  CP_TRY(fetch_async(ctx, open.data(), d_open, open.size() * 16));
-
-  // ---- the FRI opening proof: PolynomialBatch::prove_openings over the four oracles, batches at zeta and g*zeta ------
-  std::vector<OracleRef> oracles(4);
-  oracles[0].k = k_cs;
-  oracles[0].t_coeffs = t_coeffs; oracles[0].t_lde = t_lde; oracles[0].t_dig = t_dig;
-  for (int b = 1; b < 4; b++) {
-    OracleRef &O = oracles[b];
-    O.k = B[b].k;
-    O.coeffs = B[b].coeffs; O.lde = B[b].lde; O.digests = B[b].digests;
-    O.coeffs_stride = B[b].coeffs_stride; O.lde_stride = B[b].lde_stride; O.dig_stride = B[b].dig_stride;
-    O.salt = B[b].salt; O.salt_stride = B[b].salt_stride; O.n_salt = B[b].n_salt;
-  }
-  std::vector<FriBatchDesc> fbatches(2);  // plonky2 `FRI_ORACLES` / `fri_instance`: everything at zeta, the Z polynomials at g*zeta
-  fbatches[0].ranges = {{0, 0, (uint32_t)k_cs}, {1, 0, (uint32_t)k_w}, {2, 0, (uint32_t)k_z}, {3, 0, (uint32_t)k_q}};
-  fbatches[0].n_polys = k_all;
-  fbatches[1].ranges = {{2, 0, (uint32_t)nc}};
-  fbatches[1].n_polys = (size_t)nc;
-  FriCfg cfg;
-  cfg.rate_bits = rb; cfg.cap_height = ch; cfg.pow_bits = sh.pow_bits; cfg.num_query_rounds = sh.num_query_rounds; cfg.n_arity = sh.n_arity;
-  for (int l = 0; l < 8; l++) cfg.arity_bits[l] = sh.arity_bits[l];
+  std::vector<gl::Ext> open;
+  CP_TRY(tail_openings(ctx, Bn, nc, D, t, B, d_pts, &zpow, &d_open, open));
   FriHostOut fri_out;
-  // observe_openings: the zeta batch, then zs_next — exactly the layout of d_open
-  const tr::Seg opened{(const uint64_t *)d_open, nullptr, open_stride * 2, (uint32_t)(open_stride * 2)};
-  CP_TRY(fri_prove_impl(ctx, Bn, db, cfg, oracles, fbatches, zpow, zinv, T, opened, use_pow, pow_ov, d_flags, fri_out));
+  CP_TRY(tail_fri(ctx, Bn, sh, D, t, B, zpow, d_open, T, use_pow, pow_ov, fri_out));
 
   host_phase(ctx, "drain");
   CP_TRY(fetch_flush(ctx));  // the one synchronisation of the call
   CP_TRY(fri_out.check(ctx));
 
   host_phase(ctx, "bincode");
-  // ---- bincode ProofWithPublicInputs ------------------------------------------------------------------
-  outs.resize(Bn);
-  for (size_t p = 0; p < Bn; p++) {
-    ByteBuf &out = outs[p];
-    out.v.reserve(8 * ((size_t)cfg.num_query_rounds * fri_out.words + 8192 + n_pis[p]));
-    for (int b = 1; b <= 3; b++) { out.u64(cap_n); out.felts(B[b].cap_host.data() + p * cap_n * 4, cap_n * 4); }
-    const uint64_t *o = (const uint64_t *)(open.data() + p * open_stride);
-    size_t pos = 0;
-    auto put = [&](size_t cnt, size_t at) { out.u64(cnt); out.felts(o + 2 * at, 2 * cnt); };
-    put(sh.num_constants, pos); pos += sh.num_constants;
-    put(sh.num_routed_wires, pos); pos += sh.num_routed_wires;
-    put(k_w, pos); pos += k_w;
-    put(nc, pos);               // plonk_zs
-    put(nc, k_all);             // plonk_zs_next
-    put(k_z - nc, pos + nc);    // partial_products
-    pos += k_z;
-    put(k_q, pos);
-    out.u64(0); out.u64(0);     // lookup_zs, lookup_zs_next
-    fri_out.bytes(p, out);      // FriProof
-    out.u64(n_pis[p]); out.felts(pis[p], n_pis[p]);
-  }
+  tail_encode(Bn, sh, D, B, open, fri_out, pis, n_pis, outs);
   return CP_OK;
 }
 

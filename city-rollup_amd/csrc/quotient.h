@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void k_quot_arith_group(Args a, ArithGroup G, 
 // points, all at the same time, reading wires from LDS; the partial sums meet in LDS (the tile's memory, reused), are divided by
 // Z_H and written to the point's natural position: the accumulator array, its read-modify-write per launch and k_quot_finish are
 // gone as well. The pieces are ordered so that the waves a SIMD receives (wave w of a workgroup runs on SIMD w mod 4) carry about
-// the same work (prover_tail.inc: longest piece first onto the lightest SIMD). One workgroup per CU (the heaviest gate's registers
+// the same work (quotient.inc quot_tile_plan: longest piece first onto the lightest SIMD). One workgroup per CU (the heaviest gate's registers
 // for every wave, at most 128: four waves per SIMD). Field addition is exact: the same bits whatever the split.
 struct TilePieces {
   int n;            // waves with a piece

@@ -155,25 +155,14 @@ int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::
   if (n_spill) CP_TRY(arena_alloc(ctx, (size_t)n_spill * ka.spill_stride * 8, (void **)&ka.spill));
   const size_t lds_bytes = (size_t)(n_lds ? n_lds : 1) * K * air::WAVE * 8;
   if (blocks > 0x7FFFFFFFull || S > 65535) return set_error(ctx, CP_ERR_UNSUPPORTED, "AIR launch too large");
-  cp_ctx::ProfRec pr{name, nullptr, nullptr};
-  if (ctx->profiling) {
-    pr.e0 = prof_event(ctx);
-    pr.e1 = prof_event(ctx);
-    (void)hipEventRecord(pr.e0, ctx->stream);
-  }
   const dim3 grid((unsigned)blocks, S), block(air::WAVE);
-#define CP_AIR_LAUNCH(MODE, KP) hipLaunchKernelGGL((air::k_run<MODE, KP>), grid, block, lds_bytes, ctx->stream, ka)
+#define CP_AIR_LAUNCH(MODE, KP) LAUNCH_LDS(ctx, name, (air::k_run<MODE, KP>), grid, block, lds_bytes, ka)
   if (map_mode) {
     if (K == 4) CP_AIR_LAUNCH(1, 4); else if (K == 2) CP_AIR_LAUNCH(1, 2); else CP_AIR_LAUNCH(1, 1);
   } else {
     if (K == 4) CP_AIR_LAUNCH(0, 4); else if (K == 2) CP_AIR_LAUNCH(0, 2); else CP_AIR_LAUNCH(0, 1);
   }
 #undef CP_AIR_LAUNCH
-  if (ctx->profiling) {
-    (void)hipEventRecord(pr.e1, ctx->stream);
-    ctx->prof_recs.push_back(pr);
-  }
-  HIP_TRY(ctx, hipGetLastError());
   return CP_OK;
 }
 

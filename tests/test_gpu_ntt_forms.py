@@ -7,6 +7,9 @@ it: the natural-order LDS epilogue at 2^12, the bit-reversal copy, the staged st
 and the generic kernel at >= 2^12 under CITYPROVER_NTT_V1. `ntt_plan` restates the planner; every case asserts the launches it
 predicts. The GPU is touched only inside tests."""
 import collections
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +18,7 @@ import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
 P = O.P
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LOG_TILE = 12           # ntt.h LOG_TILE_MAX == ntt16.h LOG_TILE
 INVERSE, BITREV_OUT, COSET = 1, 2, 4   # cityprover.NTT_*
 EDGE = np.array([0, 1, 2, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0xFFFFFFFF00000000, 0xFFFFFFFE00000002, 1 << 63, P >> 1, 7],
@@ -214,9 +218,8 @@ def test_padded_lde_matches_oracle(prover, log_n, rate, bitrev):
     assert launches == lde_plan(log_n, rate, bitrev), dict(launches)
 
 
-def test_legacy_generic_kernel_at_4096_and_up(prover, monkeypatch):
-    """CITYPROVER_NTT_V1 (read on every call): the generic kernel instead of radix-16 wherever the caller does not need the latter"""
-    monkeypatch.setenv("CITYPROVER_NTT_V1", "1")
+def legacy_generic_kernel_checks(prover):
+    """the body of test_legacy_generic_kernel_at_4096_and_up: runs in a process started with CITYPROVER_NTT_V1 set"""
     for log_n in range(13, 18):
         x = inputs(log_n)
         for flags in (0, INVERSE):
@@ -234,3 +237,24 @@ def test_legacy_generic_kernel_at_4096_and_up(prover, monkeypatch):
     got, launches = call(prover, prover.ntt, x)
     assert (got[0] == O.ntt(x[0])).all()
     assert launches == {"ntt16_rows": 1}
+
+
+CHILD = r"""
+import sys
+sys.path[:0] = [{tests!r}, {pkg!r}]
+import cityprover
+import test_gpu_ntt_forms as T
+p = cityprover.Prover(0)
+T.legacy_generic_kernel_checks(p)
+p.close()
+print("ntt v1 ok")
+"""
+
+
+def test_legacy_generic_kernel_at_4096_and_up():
+    """CITYPROVER_NTT_V1 (read once per process, a function-static): the generic kernel instead of radix-16 wherever the caller
+    does not need the latter, in a fresh child"""
+    env = dict(os.environ, CITYPROVER_NTT_V1="1")
+    code = CHILD.format(tests=os.path.join(ROOT, "tests"), pkg=os.path.join(ROOT, "city-rollup_amd"))
+    r = subprocess.run([sys.executable, "-c", code], env=env, timeout=300, capture_output=True, text=True)
+    assert r.returncode == 0 and "ntt v1 ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

@@ -18,7 +18,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 QBENCH_SOURCES = ["gl.h", "poseidon.h", "poseidon_tables.h", "poseidon_coop.h", "merkle.h", "ntt.h", "ntt16.h", "fri.h", "zs.h", "quotient.h", "gates.h",
-                  "prover_tail.inc", "fri_engine.inc"]
+                  "quotient.inc", "prover_tail.inc", "fri_engine.inc"]
 N_LDE, NC, N_CONST, N_ROUTED, N_WIRES, N_ZS = 1 << 15, 2, 5, 80, 135, 20   # the product shape
 GATE_NAMES = ["noop", "constant", "public_input", "arithmetic", "poseidon", "comparison", "u32_arithmetic", "u32_range_check", "u32_add_many",
               "u32_subtraction", "u32_interleave", "uninterleave_to_u32", "uninterleave_to_b32", "arithmetic_ext", "mul_ext", "base_sum",
