@@ -48,6 +48,40 @@ uint64_t hs_mul(uint64_t a, uint64_t b) { return gl::mul(a, b); }
 uint64_t hs_mul_lazy(uint64_t a, uint64_t b) { return poseidon::mul_lazy(a, b); }
 uint64_t hs_add(uint64_t a, uint64_t b) { return gl::add(a, b); }
 uint64_t hs_sub(uint64_t a, uint64_t b) { return gl::sub(a, b); }
+// which rare paths a * b takes in reduce128_lazy / fold_top (tests/rare_paths.py restates this with Python integers):
+// bit 0 = the borrow of `lo - w3`, bit 1 = the wrap of `+ w2 (2^32 - 1)`, bit 2 = the lazy result is >= p (canon matters)
+int hs_mul_paths(uint64_t a, uint64_t b) {
+  uint64_t lo, hi;
+  gl::mul_wide(a, b, lo, hi);
+  const uint32_t w2 = gl::lo32(hi), w3 = gl::hi32(hi);
+  const gl::u128 t = (gl::u128)lo - w3;
+  const int borrow = (uint64_t)(t >> 64) != 0;
+  const uint64_t t0 = (uint64_t)t - ((uint64_t)(t >> 64) & gl::EPS);
+  const gl::u128 s = (gl::u128)t0 + (((uint64_t)w2 << 32) - w2);
+  const int wrap = (uint64_t)(s >> 64) != 0;
+  const uint64_t lazy = gl::reduce128_lazy(lo, hi);
+  if (lazy != gl::fold_top(t0, w2)) return -1;  // the pieces above are the ones reduce128_lazy is made of
+  return borrow | wrap << 1 | (lazy >= gl::P) << 2;
+}
+// `permute_until` composed from the same layers, WITHOUT the final canon: the lazy state the device canonicalises on its way out
+void hs_poseidon_permute_lazy(uint64_t *states, size_t n) {
+  using namespace poseidon;
+  for (size_t i = 0; i < n; i++) {
+    uint64_t s[W];
+    for (int k = 0; k < W; k++) s[k] = add_const_lazy(states[W * i + k], rc(k));
+    for (int r = 0; r < HALF_FULL - 1; r++) {
+      for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);
+      mds_layer_d(s, (r + 1) * W);
+    }
+    for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);
+    partial_rounds(s, SameInput(), NeverStop());
+    for (int r = HALF_FULL + PARTIAL; r < ROUNDS; r++) {
+      for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);
+      mds_layer_d(s, r + 1 < ROUNDS ? (r + 1) * W : -1);
+    }
+    for (int k = 0; k < W; k++) states[W * i + k] = s[k];
+  }
+}
 void hs_mds_limb(const uint32_t *s, uint32_t *y) {
   uint32_t a[12], b[12];
   for (int i = 0; i < 12; i++) a[i] = s[i];
