@@ -259,14 +259,24 @@ __global__ __launch_bounds__(256) void k_leaf_hash_fri(const uint64_t *__restric
   if (len <= 4) {
     for (int e = 0; e < len; e++) s[e] = (e & 1) ? im[arity * j + (e >> 1)] : re[arity * j + (e >> 1)];
   } else {
-    for (int e0 = 0; e0 < len; e0 += poseidon::RATE) {
+    // arity = 1 << arity_bits, so a hashed leaf (len = 8, 16, 32, 64) is whole chunks: every permutation but the last keeps
+    // only the capacity, the last gives the digest (poseidon.h; one call per form)
+    int e0 = 0;
+#pragma unroll 1
+    for (; e0 + poseidon::RATE < len; e0 += poseidon::RATE) {
 #pragma unroll
       for (int k = 0; k < poseidon::RATE; k++) {
         int e = e0 + k;
-        if (e < len) s[k] = (e & 1) ? im[arity * j + (e >> 1)] : re[arity * j + (e >> 1)];
+        s[k] = (e & 1) ? im[arity * j + (e >> 1)] : re[arity * j + (e >> 1)];
       }
-      poseidon::permute(s);
+      poseidon::permute_absorb(s);
     }
+#pragma unroll
+    for (int k = 0; k < poseidon::RATE; k++) {
+      int e = e0 + k;
+      s[k] = (e & 1) ? im[arity * j + (e >> 1)] : re[arity * j + (e >> 1)];
+    }
+    poseidon::permute_squeeze(s);
   }
   uint64_t *d = digests + (size_t)blockIdx.y * dig_stride + 4 * j;
   d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];

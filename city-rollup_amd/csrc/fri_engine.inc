@@ -256,6 +256,8 @@ int fri_prove_impl(cp_ctx *ctx, size_t Bn, int db, const FriCfg &cfg, const std:
   for (int l = 0; l < cfg.n_arity; l++) {
     Layer &L = layers[l];
     const int ab = cfg.arity_bits[l], arity = 1 << ab;
+    // k_leaf_hash_fri reads a hashed leaf (more than four words) as whole chunks, without a bound on the last one
+    if (2 * arity > 4 && (2 * arity) % poseidon::RATE) return set_error(ctx, CP_ERR_INTERNAL, "FRI leaf of %d words is not whole sponge chunks", 2 * arity);
     L.vals = vals;
     L.n_vals = clen;
     L.n_leaves = clen >> ab;

@@ -216,11 +216,11 @@ def perm_fast(s, RC, tabs):
     return s
 
 
-def c_array(name, vals, per_line=4, ctype="uint64_t"):
+def c_array(name, vals, per_line=4, ctype="uint64_t", qualifier="const"):
     body = ""
     for i in range(0, len(vals), per_line):
         body += "    " + ", ".join(f"0x{v:016x}ULL" for v in vals[i:i + per_line]) + ",\n"
-    return f"static const {ctype} {name}[{len(vals)}] = {{\n{body}}};\n"
+    return f"static {qualifier} {ctype} {name}[{len(vals)}] = {{\n{body}}};\n"
 
 
 def main():
@@ -279,6 +279,8 @@ def main():
     out += c_array("POSEIDON_RCD", magic_pairs([(k - biasd) % P for k in RC] + [(-biasd) % P]))  # [2 * 360 ..] = no constant
     out += c_array("POSEIDON_DOMD_K", magic_pairs([(k - biasd) % P for k in DK]))
     out += c_array("POSEIDON_DOMD_LAST", magic_pairs([(k - biasd) % P for k in DLAST]))
+    out += "// round 0 of a capacity word that is zero on entry (poseidon.h `ZERO_CAP`): (0 + RC[8 + i])^7, canonical\n"
+    out += c_array("POSEIDON_CAP0_SBOX", [pow(RC[8 + i], 7, P) for i in range(4)], qualifier="constexpr")
     out += "// primitive 2^k-th roots of unity, k = 0..32 (7^((p-1)/2^k))\n"
     out += c_array("GL_ROOTS", roots)
     out += c_array("GL_ROOTS_INV", [pow(r, P - 2, P) for r in roots])

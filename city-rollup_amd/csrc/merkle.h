@@ -46,9 +46,7 @@ __device__ __forceinline__ void fused_levels(uint64_t *sd, const uint64_t (&own)
     }
     __syncthreads();  // every child pair is in registers before a parent overwrites LDS
     if (t < cnt) {
-#pragma unroll
-      for (int k = 8; k < poseidon::W; k++) s[k] = 0;
-      poseidon::permute(s);
+      poseidon::permute_node(s);
       uint64_t *d = digests + off + 4 * ((first_node >> l) + t);
 #pragma unroll
       for (int k = 0; k < 4; k++) { d[k] = s[k]; sd[4 * t + k] = s[k]; }
@@ -62,8 +60,9 @@ __device__ __forceinline__ void fused_levels(uint64_t *sd, const uint64_t (&own)
 // elements read from a second column-major array (salt + t*salt_tree_stride, column stride = col_stride).
 // FUSE > 0: the workgroup also computes the next FUSE levels of its subtree (fused_levels); n_leaves must then be a multiple of
 // THREADS and the levels must lie below the cap.
-template <bool SALT, int FUSE = 0>
-__global__ __launch_bounds__(THREADS, 5) void k_leaf_hash_cols(const uint64_t *__restrict__ cols,
+// RESIDENT: workgroups per CU the register budget is sized for (5: 96 registers; 4: 128).
+template <bool SALT, int FUSE = 0, int RESIDENT = 5>
+__global__ __launch_bounds__(THREADS, RESIDENT) void k_leaf_hash_cols(const uint64_t *__restrict__ cols,
                                                             size_t n_leaves, int leaf_len,
                                                             size_t col_stride,
                                                             uint64_t *__restrict__ digests,
@@ -88,18 +87,28 @@ __global__ __launch_bounds__(THREADS, 5) void k_leaf_hash_cols(const uint64_t *_
   if (total <= 4) {
     for (int j = 0; j < total; j++) s[j] = elem(j);
   } else {
+    // one call per form (poseidon.h): chunks whose successor overwrites all eight rate words keep only the capacity; the
+    // chunk before a PARTIAL last one keeps everything (the words that one leaves alone are absorbed again); the last gives
+    // the digest. (The zero capacity of the first chunk is not used: a fourth copy of the code for 4 of 135 S-boxes.)
+    const int rem = total % poseidon::RATE;
+    const int n_absorb = (total - 1) / poseidon::RATE - (rem ? 1 : 0);  // all but the last, and but the one before a partial last
     int j = 0;
-    for (; j + poseidon::RATE <= total; j += poseidon::RATE) {
+#pragma unroll 1
+    for (int c = 0; c < n_absorb; c++, j += poseidon::RATE) {
+#pragma unroll
+      for (int k = 0; k < poseidon::RATE; k++) s[k] = elem(j + k);
+      poseidon::permute_absorb(s);
+    }
+    if (rem && total > poseidon::RATE) {
 #pragma unroll
       for (int k = 0; k < poseidon::RATE; k++) s[k] = elem(j + k);
       poseidon::permute(s);
+      j += poseidon::RATE;
     }
-    if (j < total) {  // partial last chunk overwrites only its own lanes (overwrite-mode sponge)
 #pragma unroll
-      for (int k = 0; k < poseidon::RATE; k++)
-        if (j + k < total) s[k] = elem(j + k);
-      poseidon::permute(s);
-    }
+    for (int k = 0; k < poseidon::RATE; k++)
+      if (j + k < total) s[k] = elem(j + k);  // a partial last chunk overwrites only its own lanes (overwrite-mode sponge)
+    poseidon::permute_squeeze(s);
   }
   uint64_t *d = digests + 4 * i;
   d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
@@ -148,9 +157,7 @@ __global__ __launch_bounds__(THREADS) void k_level(const uint64_t *__restrict__ 
   const uint64_t *c = child + 8 * i;
 #pragma unroll
   for (int k = 0; k < 8; k++) s[k] = c[k];
-#pragma unroll
-  for (int k = 8; k < poseidon::W; k++) s[k] = 0;
-  poseidon::permute(s);
+  poseidon::permute_node(s);
   uint64_t *d = parent + 4 * i;
   d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
 }
@@ -167,9 +174,7 @@ __global__ __launch_bounds__(THREADS, 5) void k_level_fused(uint64_t *__restrict
   const uint64_t *c = D + child_off + 8 * i;
 #pragma unroll
   for (int k = 0; k < 8; k++) s[k] = c[k];
-#pragma unroll
-  for (int k = 8; k < poseidon::W; k++) s[k] = 0;
-  poseidon::permute(s);
+  poseidon::permute_node(s);
   uint64_t *lvl = D + child_off + 8 * n_parents;  // this level sits right behind its children
   uint64_t *d = lvl + 4 * i;
   d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
@@ -186,9 +191,7 @@ __global__ __launch_bounds__(THREADS) void k_two_to_one(const uint64_t *__restri
   uint64_t s[poseidon::W];
 #pragma unroll
   for (int k = 0; k < 4; k++) { s[k] = left[4 * i + k]; s[4 + k] = right[4 * i + k]; }
-#pragma unroll
-  for (int k = 8; k < poseidon::W; k++) s[k] = 0;
-  poseidon::permute(s);
+  poseidon::permute_node(s);
 #pragma unroll
   for (int k = 0; k < 4; k++) out[4 * i + k] = s[k];
 }

@@ -67,6 +67,19 @@ GL_HD Magic domd_last(int i) {
   return {__builtin_bit_cast(double, POSEIDON_DOMD_LAST[2 * i]), __builtin_bit_cast(double, POSEIDON_DOMD_LAST[2 * i + 1])};
 #endif
 }
+// ---- what a caller keeps of a permutation, and what it knows of its input --------------------------------------------------
+// `hash_no_pad` is an overwrite-mode sponge: the rate words 0..7 of every permutation but a leaf's last are overwritten by the
+// next chunk, and of the last one (and of a tree node's only one) words 0..3 are the digest. `permute_until<OUT, ZERO_CAP>`:
+// OUT says which outputs are live — the last layer leaves the transformed domain, recombines and canonicalises only those, and
+// clears the others — and ZERO_CAP that the capacity words 8..11 of the input are known to be zero (every tree node, the first
+// permutation of a leaf): their first round is then four table constants (POSEIDON_CAP0_SBOX = (0 + rc[8 + i])^7) and what `s`
+// holds there is not read. Both are compile-time: with the form in registers the leaf hash spilled 30-50 registers where it
+// spills 6, so a sponge loop has one call per form it needs (merkle.h k_leaf_hash_cols).
+enum : int {
+  OUT_ALL = 0,       // all twelve, canonical
+  OUT_CAPACITY = 1,  // words 8..11, lazy (any u64 congruent to the value: what the next permutation's `add_const_lazy` takes)
+  OUT_DIGEST = 2     // words 0..3, canonical
+};
 // ---- lazy field helpers: inputs/outputs are arbitrary u64 congruent to the value ----------
 using gl::fold_top;
 GL_HD uint64_t mul_lazy(uint64_t a, uint64_t b) {
@@ -288,6 +301,18 @@ GL_HD uint64_t recombine_d(double l, double h, Magic m) {
   return fold_top(gl::pack(gl::lo32(a0), w1), gl::hi32(a1) + carry);
 }
 
+// the butterflies back for the live words only: y[0..3] = words 0..3 (digest) or words 8..11 (capacity)
+GL_HD void dom_leave_digest_d(const double (&o)[W], double (&y)[4]) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) y[i] = (o[i] + o[3 + i]) + o[6 + i];
+  y[3] = (o[0] - o[3]) + o[9];
+}
+GL_HD void dom_leave_capacity_d(const double (&o)[W], double (&y)[4]) {
+  y[0] = (o[2] + o[5]) - o[8];
+#pragma unroll
+  for (int i = 0; i < 3; i++) y[1 + i] = (o[i] - o[3 + i]) - o[9 + i];
+}
+
 // s <- MDS * s + next_rc on two double-precision limb planes (next_rc_base < 0: no constant)
 GL_HD void mds_layer_d(uint64_t (&s)[W], int next_rc_base) {
   double ll[W], lh[W], u[W], o[W], yl[W], yh[W];
@@ -307,7 +332,41 @@ GL_HD void mds_layer_d(uint64_t (&s)[W], int next_rc_base) {
 #pragma unroll
   for (int i = 0; i < W; i++) s[i] = recombine_d(yl[i], yh[i], rcd(next_rc_base >= 0 ? next_rc_base + i : ROUNDS * W));
 }
-
+// The permutation's LAST layer (no constant follows it) for a form that keeps four words: only those leave the domain and are
+// recombined (the products nobody reads go with them). The dead words are cleared.
+template <bool DIGEST>
+GL_HD void mds_last_layer_d(uint64_t (&s)[W]) {
+  double ll[W], lh[W], u[W], o[W], yl[4], yh[4];
+#pragma unroll
+  for (int i = 0; i < W; i++) {
+    ll[i] = (double)(uint32_t)s[i];
+    lh[i] = (double)(uint32_t)(s[i] >> 32);
+  }
+  dom_enter_d(ll, u);
+  dom_mul_d<false>(u, o);
+  if (DIGEST) {
+    dom_leave_digest_d(o, yl);
+    yl[0] = __builtin_fma(ll[0], 8.0, yl[0]);
+  } else {
+    dom_leave_capacity_d(o, yl);
+  }
+  dom_enter_d(lh, u);
+  dom_mul_d<false>(u, o);
+  if (DIGEST) {
+    dom_leave_digest_d(o, yh);
+    yh[0] = __builtin_fma(lh[0], 8.0, yh[0]);
+  } else {
+    dom_leave_capacity_d(o, yh);
+  }
+  const Magic none = rcd(ROUNDS * W);
+#pragma unroll
+  for (int i = 0; i < W; i++) s[i] = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if (DIGEST) s[i] = gl::canon(recombine_d(yl[i], yh[i], none));
+    else s[RATE + i] = recombine_d(yl[i], yh[i], none);
+  }
+}
 // ---- the scaled layer two deep (partial_rounds): constants derived from dom_mul_d<true> at compile time ------------------------
 template <int N> struct DomMat { double a[N][N]; };
 template <int N> constexpr DomMat<N> dom_mat_sq(const DomMat<N> &m) {
@@ -444,7 +503,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
     nl = (double)(uint32_t)x;
     nh = (double)(uint32_t)(x >> 32);
     dom_mul2_d(al, nl - zl, bl);
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(POSEIDON_INTERLEAVE_PLANES)  // the macro: A/B in tools/ubench_leaf_residency.hip
     __builtin_amdgcn_sched_barrier(0);  // one plane after the other: interleaved, the four arrays are live at once and the leaf hash (96 registers) spills
 #endif
     dom_mul2_d(ah, nh - zh, bh);
@@ -474,29 +533,45 @@ struct SameInput {
 // `stop` is polled between rounds (every full round, every fourth partial round); when it answers true the permutation is
 // abandoned and false returned. It must answer the same for every lane of a wave. The proof-of-work search uses it to drop
 // candidates that can no longer be the smallest witness.
-template <typename Stop>
+template <int OUT = OUT_ALL, bool ZERO_CAP = false, typename Stop>
 GL_HD bool permute_until(uint64_t (&s)[W], Stop stop) {
+  static_assert(OUT == OUT_ALL || OUT == OUT_CAPACITY || OUT == OUT_DIGEST, "unknown output form");
 #pragma unroll
-  for (int i = 0; i < W; i++) s[i] = add_const_lazy(s[i], rc(i));
+  for (int i = 0; i < RATE; i++) s[i] = add_const_lazy(s[i], rc(i));
+#pragma unroll
+  for (int i = RATE; i < W; i++) s[i] = ZERO_CAP ? POSEIDON_CAP0_SBOX[i - RATE] : add_const_lazy(s[i], rc(i));  // round 0 of a zero word: done offline
 #pragma unroll 1
   for (int r = 0; r < HALF_FULL - 1; r++) {
     if (stop()) return false;
 #pragma unroll
-    for (int i = 0; i < W; i++) s[i] = sbox_lazy(s[i]);
+    for (int i = 0; i < RATE; i++) s[i] = sbox_lazy(s[i]);
+    if (r > 0 || !ZERO_CAP) {
+#pragma unroll
+      for (int i = RATE; i < W; i++) s[i] = sbox_lazy(s[i]);
+    }
     mds_layer_d(s, (r + 1) * W);
   }
 #pragma unroll
   for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);  // the last full round before the partial rounds
   if (!partial_rounds(s, SameInput(), stop)) return false;
+  // a form that drops outputs has its last round apart from the loop (its layer is another one); OUT_ALL keeps the loop whole
+  constexpr int LOOPED = OUT == OUT_ALL ? ROUNDS : ROUNDS - 1;
 #pragma unroll 1
-  for (int r = HALF_FULL + PARTIAL; r < ROUNDS; r++) {
+  for (int r = HALF_FULL + PARTIAL; r < LOOPED; r++) {
     if (stop()) return false;
 #pragma unroll
     for (int i = 0; i < W; i++) s[i] = sbox_lazy(s[i]);
     mds_layer_d(s, r + 1 < ROUNDS ? (r + 1) * W : -1);
   }
+  if (OUT == OUT_ALL) {
 #pragma unroll
-  for (int i = 0; i < W; i++) s[i] = gl::canon(s[i]);
+    for (int i = 0; i < W; i++) s[i] = gl::canon(s[i]);
+  } else {
+    if (stop()) return false;
+#pragma unroll
+    for (int i = 0; i < W; i++) s[i] = sbox_lazy(s[i]);
+    mds_last_layer_d<OUT == OUT_DIGEST>(s);
+  }
   return true;
 }
 
@@ -504,6 +579,11 @@ struct NeverStop {
   GL_HD bool operator()() const { return false; }
 };
 GL_HD void permute(uint64_t (&s)[W]) { permute_until(s, NeverStop()); }
+// the only permutation of a tree node (two_to_one): zero capacity in, digest out
+GL_HD void permute_node(uint64_t (&s)[W]) { permute_until<OUT_DIGEST, true>(s, NeverStop()); }
+// of a sponge chain: a permutation whose rate words the next chunk overwrites whole; the last one
+GL_HD void permute_absorb(uint64_t (&s)[W]) { permute_until<OUT_CAPACITY, false>(s, NeverStop()); }
+GL_HD void permute_squeeze(uint64_t (&s)[W]) { permute_until<OUT_DIGEST, false>(s, NeverStop()); }
 // What HOST code hashes with (the transcript of a small batch, the verifier, public-input hashes): the integer round structure.
 // On an x86 core it takes 1.8 us per permutation; `permute`, whose double-precision layers are shaped for the GPU's issue
 // rates, takes 5.7 us there. Same function, bit for bit (tests compare the two over 600 M chained permutations).
