@@ -185,6 +185,69 @@ int hs_bls_lz_maybe_zero(const uint32_t *a) {
   return bls::lz_maybe_zero(x) ? 1 : 0;
 }
 }
+// ---- what tests/bls_rare_paths.py restates, on raw limbs -------------------------------------------------------------
+#include <cstring>
+// one xyzz_add_mixed_loose: acc = x, y, zz, zzz as raw 28-bit limbs (NL per F_p component), q canonical words. Returns which
+// way the addition went, decided with the same primitives the addition itself uses:
+// 0 first point, 1 loose general, 2 doubling, 3 cancellation, 4 loose general after the filter passed on a non-zero difference
+template <class F>
+static int hs_loose_step(const uint32_t *acc_limbs, const uint32_t *q_xy, uint32_t *out_limbs) {
+  using B = bls::LooseBound<F>;
+  bls::XyzzT<F> p;
+  static_assert(sizeof(p) == 4 * sizeof(F) && sizeof(F) % sizeof(bls::Fp) == 0, "an accumulator is nothing but limbs");
+  memcpy(&p, acc_limbs, sizeof p);
+  const bls::AffineT<F> q = bls::affine_from_canonical<F>(q_xy);
+  int way = 0;
+  if (!bls::f_is_zero(p.zz)) {
+    const F pp_ = bls::lf_sub<B::X>(bls::lf_mul(q.x, p.zz), p.x);
+    const bool maybe = bls::lf_maybe_zero(pp_), zero = bls::f_is_zero(bls::lf_canon(pp_));
+    if (zero) way = bls::f_eq(bls::lf_canon(p.y), bls::f_mul(q.y, bls::lf_canon(p.zzz))) ? 2 : 3;
+    else way = maybe ? 4 : 1;
+    if (zero && !maybe) way = -1;  // the filter is a necessary condition
+  }
+  const bls::XyzzT<F> r = bls::xyzz_add_mixed_loose(p, q);
+  memcpy(out_limbs, &r, sizeof r);
+  return way;
+}
+// the accumulator as the kernels hand it on: canonical affine words; returns 1 for infinity
+template <class F>
+static int hs_loose_out(const uint32_t *acc_limbs, uint32_t *out_xy) {
+  bls::XyzzT<F> p;
+  memcpy(&p, acc_limbs, sizeof p);
+  return bls::jac_to_affine_canonical(bls::xyzz_to_jac_loose(p), out_xy) ? 1 : 0;
+}
+extern "C" {
+int hs_bls_g1_loose_step(const uint32_t *acc, const uint32_t *q_xy, uint32_t *out) { return hs_loose_step<bls::Fp>(acc, q_xy, out); }
+int hs_bls_g2_loose_step(const uint32_t *acc, const uint32_t *q_xy, uint32_t *out) { return hs_loose_step<bls::Fp2>(acc, q_xy, out); }
+int hs_bls_g1_loose_out(const uint32_t *acc, uint32_t *out_xy) { return hs_loose_out<bls::Fp>(acc, out_xy); }
+int hs_bls_g2_loose_out(const uint32_t *acc, uint32_t *out_xy) { return hs_loose_out<bls::Fp2>(acc, out_xy); }
+// raw limbs in, raw limbs out: op 0 fp_mul, 1 lz_mul, 2 lz_sqr (of a), 3 fp_sqr_mont (of a), 4 lz_add_nc
+void hs_bls_fp_raw(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
+  bls::Fp x, y, r;
+  for (int i = 0; i < bls::NL; i++) x.l[i] = a[i], y.l[i] = b[i];
+  switch (op) {
+    case 0: r = bls::fp_mul(x, y); break;
+    case 1: r = bls::lz_mul(x, y); break;
+    case 2: r = bls::lz_sqr(x); break;
+    case 3: r = bls::fp_sqr_mont(x); break;
+    default: r = bls::lz_add_nc(x, y); break;
+  }
+  for (int i = 0; i < bls::NL; i++) out[i] = r.l[i];
+}
+// lz_sub<K> / lz_weak<K> for every K the two accumulations use; returns -1 for any other
+#define HS_K(K) case K: r = weak ? bls::lz_weak<K>(x) : bls::lz_sub<K>(x, y); break;
+int hs_bls_lz_k(int weak, int K, const uint32_t *a, const uint32_t *b, uint32_t *out) {
+  bls::Fp x, y, r;
+  for (int i = 0; i < bls::NL; i++) x.l[i] = a[i], y.l[i] = b[i];
+  switch (K) {
+    HS_K(2) HS_K(4) HS_K(6) HS_K(8) HS_K(10) HS_K(12) HS_K(16) HS_K(18) HS_K(22)
+    default: return -1;
+  }
+  for (int i = 0; i < bls::NL; i++) out[i] = r.l[i];
+  return 0;
+}
+#undef HS_K
+}
 extern "C" {
 int hs_bls_g1_op(int op, const uint32_t *p_xy, int p_inf, const uint32_t *q_xy, int q_inf, uint32_t k, uint32_t *out_xy) {
   return hs_group_op<bls::Fp>(op, p_xy, p_inf, q_xy, q_inf, k, out_xy);
@@ -208,6 +271,30 @@ void hs_bls_fr_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
     default: r = blsfr::fr_pow_u64(x, ((uint64_t)b[1] << 32) | b[0]); break;
   }
   blsfr::fr_to_canonical(r, out);
+}
+// raw limbs in, raw limbs out: op 0 fr_mul, 1 fr_add, 2 fr_sub, 3 fr_from_canonical (a: 8 words)
+void hs_bls_fr_raw(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
+  blsfr::Fr x = blsfr::fr_zero(), y, r;
+  if (op != 3) for (int i = 0; i < blsfr::NL; i++) x.l[i] = a[i];
+  for (int i = 0; i < blsfr::NL; i++) y.l[i] = b[i];
+  switch (op) {
+    case 0: r = blsfr::fr_mul(x, y); break;
+    case 1: r = blsfr::fr_add(x, y); break;
+    case 2: r = blsfr::fr_sub(x, y); break;
+    default: r = blsfr::fr_from_canonical(a); break;
+  }
+  for (int i = 0; i < blsfr::NL; i++) out[i] = r.l[i];
+}
+}
+
+// ---- r1cs.h: the one-limb product ----
+#include "../../city-rollup_amd/csrc/r1cs.h"
+extern "C" {
+void hs_r1cs_mul_small(const uint32_t *w, uint32_t c, uint32_t *out) {
+  blsfr::Fr x, r;
+  for (int i = 0; i < blsfr::NL; i++) x.l[i] = w[i];
+  r = r1cs::mul_small(x, c);
+  for (int i = 0; i < blsfr::NL; i++) out[i] = r.l[i];
 }
 }
 

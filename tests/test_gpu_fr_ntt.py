@@ -17,8 +17,13 @@ def prover():
 
 
 def fr_rand(rng, n, r):
+    """uniform below r, the values in [2^254, r) included: 255 random bits, minus r where that is needed"""
     raw = rng.integers(0, 2**64, (n, 4), dtype=np.uint64)
-    raw[:, 3] &= np.uint64((1 << 62) - 1)      # < 2^254 < r
+    raw[:, 3] &= np.uint64((1 << 63) - 1)
+    for i in np.nonzero(raw[:, 3] >= np.uint64(r >> 192))[0]:      # only these rows can be >= r
+        v = sum(int(raw[i, j]) << (64 * j) for j in range(4))
+        if v >= r:
+            raw[i] = [((v - r) >> (64 * j)) & (2**64 - 1) for j in range(4)]
     return raw
 
 

@@ -3,6 +3,7 @@ sum of scalar multiples, plus size-independent properties at sizes the oracle do
 import numpy as np
 import pytest
 
+import bls_rare_paths as B
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -229,8 +230,10 @@ def test_g2_msm_large_closed_form(prover):
     rng = np.random.default_rng(21)
     k = rng.integers(0, 2**64, (n, 4), dtype=np.uint64)
     k[:, 3] >>= np.uint64(1)
-    k[:100] = 0
-    k[:100, 0] = 1          # a heavy bucket
+    heavy = 200             # a heavy bucket: more than HEAVY << hs = 128 points of one digit (c = 13, hs = 0 at this size)
+    assert heavy > B.msm_heavy_limit(n, 13) == 128
+    k[:heavy] = 0
+    k[:heavy, 0] = 1
     ds = prover.to_device(k)
     got = P.msm_dev(ds.ptr)
     ds.free()
