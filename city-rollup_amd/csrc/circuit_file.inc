@@ -167,13 +167,12 @@ cp_circuit *cp_circuit_load_file(cp_ctx *ctx, const char *path) try {
   std::vector<uint64_t> values;
   if (P.flags & cfile::FLAG_COEFFS) {  // coefficient form: one forward NTT per polynomial gives the values the loader wants
     values.resize(P.n_polys * P.n);
-    uint64_t *d = nullptr;
-    if (dev_malloc(ctx->device, (void **)&d, values.size() * 8) != hipSuccess) { set_error(ctx, CP_ERR_OOM, "hipMalloc failed"); return nullptr; }
-    int rc = cp_h2d(ctx, d, polys, values.size() * 8);
-    if (rc == CP_OK) rc = cp_ntt_dev(ctx, d, P.sh.degree_bits, P.n_polys, P.n, 0, 0);
-    if (rc == CP_OK) rc = cp_d2h(ctx, values.data(), d, values.size() * 8);
-    (void)hipFree(d);
-    if (rc != CP_OK) return nullptr;
+    DevBuf tmp = ctx->buf();
+    if (alloc_status(ctx, tmp.alloc(values.size() * 8), values.size() * 8) != CP_OK) return nullptr;
+    uint64_t *d = tmp.get<uint64_t>();
+    if (cp_h2d(ctx, d, polys, values.size() * 8) != CP_OK || cp_ntt_dev(ctx, d, P.sh.degree_bits, P.n_polys, P.n, 0, 0) != CP_OK ||
+        cp_d2h(ctx, values.data(), d, values.size() * 8) != CP_OK)
+      return nullptr;
     polys = values.data();
   }
   cp_circuit *c = cp_circuit_load(ctx, &P.sh, P.digest, polys, (P.flags & cfile::FLAG_K_IS) ? P.k_is.data() : nullptr);

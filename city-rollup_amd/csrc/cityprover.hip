@@ -13,7 +13,7 @@ namespace {
 int get_pow_table(cp_ctx *ctx, uint64_t base, const uint64_t **out) {
   auto it = ctx->pow_tables.find(base);
   if (it != ctx->pow_tables.end()) {
-    *out = it->second.dev;
+    *out = it->second.get<uint64_t>();
     return CP_OK;
   }
   std::vector<uint64_t> h(3 * ntt::PT_SIZE);
@@ -26,13 +26,12 @@ int get_pow_table(cp_ctx *ctx, uint64_t base, const uint64_t **out) {
     }
     b = acc;  // base^(2048^(lvl+1))
   }
-  PowTable t;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&t.dev, h.size() * sizeof(uint64_t)));
-  HIP_TRY(ctx, hipMemcpyAsync(t.dev, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
-                              ctx->stream));
+  DevBuf t = ctx->buf();
+  CP_TRY(alloc_status(ctx, t.alloc(h.size() * sizeof(uint64_t)), h.size() * sizeof(uint64_t)));
+  HIP_TRY(ctx, hipMemcpyAsync(t.get(), h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // h goes out of scope
-  ctx->pow_tables[base] = t;
-  *out = t.dev;
+  *out = t.get<uint64_t>();
+  ctx->pow_tables[base] = std::move(t);
   return CP_OK;
 }
 
@@ -45,19 +44,19 @@ int get_prescale_table(cp_ctx *ctx, int log_n, int rate_bits, uint64_t shift, co
   cp_ctx::PreKey key{log_n, rate_bits, shift};
   auto it = ctx->prescale_tables.find(key);
   if (it != ctx->prescale_tables.end()) {
-    *out = it->second;
+    *out = it->second.get<uint64_t>();
     return CP_OK;
   }
   const uint64_t *stab, *wtabN;
   CP_TRY(get_pow_table(ctx, shift, &stab));
   CP_TRY(get_pow_table(ctx, root_of_unity(log_n + rate_bits, false), &wtabN));
   size_t N = (size_t)1 << (log_n + rate_bits);
-  uint64_t *T = nullptr;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&T, N * sizeof(uint64_t)));
-  LAUNCH(ctx, "lde_fill_prescale", ntt16::k_fill_prescale, dim3((unsigned)((N + 255) / 256)), dim3(256), T,
+  DevBuf T = ctx->buf();
+  CP_TRY(alloc_status(ctx, T.alloc(N * sizeof(uint64_t)), N * sizeof(uint64_t)));
+  LAUNCH(ctx, "lde_fill_prescale", ntt16::k_fill_prescale, dim3((unsigned)((N + 255) / 256)), dim3(256), T.get<uint64_t>(),
          log_n, rate_bits, stab, wtabN);
-  ctx->prescale_tables[key] = T;
-  *out = T;
+  *out = T.get<uint64_t>();
+  ctx->prescale_tables[key] = std::move(T);
   return CP_OK;
 }
 
@@ -76,21 +75,14 @@ int get_l0_table(cp_ctx *ctx, int log_n, int rate_bits, const uint64_t *omega_ta
     // filled and checked BEFORE it is cached: a failed launch (or an earlier asynchronous error surfacing here) must not
     // leave an uninitialised table behind for every later proof of this shape (once per shape and context: the sync is free)
     const size_t N = (size_t)1 << (log_n + rate_bits);
-    uint64_t *tab = nullptr;
-    HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&tab, N * 8));
-    int rc = [&]() -> int {
-      LAUNCH(ctx, "quotient_fill_l0", quot::k_fill_l0, dim3(blocks_for(N, 256)), dim3(256), tab, N, log_n + rate_bits, rate_bits, omega_tab, zh,
-             ((uint64_t)1 << log_n) % gl::P);
-      HIP_TRY(ctx, sync_stream(ctx));
-      return CP_OK;
-    }();
-    if (rc != CP_OK) {
-      (void)hipFree(tab);
-      return rc;
-    }
-    it = ctx->l0_tables.emplace(std::make_pair(log_n, rate_bits), tab).first;
+    DevBuf tab = ctx->buf();
+    CP_TRY(alloc_status(ctx, tab.alloc(N * 8), N * 8));
+    LAUNCH(ctx, "quotient_fill_l0", quot::k_fill_l0, dim3(blocks_for(N, 256)), dim3(256), tab.get<uint64_t>(), N, log_n + rate_bits, rate_bits,
+           omega_tab, zh, ((uint64_t)1 << log_n) % gl::P);
+    HIP_TRY(ctx, sync_stream(ctx));
+    it = ctx->l0_tables.emplace(std::make_pair(log_n, rate_bits), std::move(tab)).first;
   }
-  *out = it->second;
+  *out = it->second.get<uint64_t>();
   return CP_OK;
 }
 
@@ -124,7 +116,7 @@ int power_on_self_test(cp_ctx *ctx) {
     for (int k = 0; k < poseidon::W; k++) want[N + k] = s[k];
   }
   CP_TRY(ensure_scratch(ctx, (3 * N + poseidon::W) * sizeof(uint64_t)));
-  uint64_t *da = (uint64_t *)ctx->scratch, *db = da + N, *dout = db + N;
+  uint64_t *da = ctx->scratch.get<uint64_t>(), *db = da + N, *dout = db + N;
   CP_TRY(cp_h2d(ctx, da, a, sizeof a));
   CP_TRY(cp_h2d(ctx, db, b, sizeof b));
   LAUNCH(ctx, "self_test", k_self_test, dim3(1), dim3(64), da, db, dout, N);
@@ -362,7 +354,7 @@ int merkle_cols_batch(cp_ctx *ctx, const uint64_t *cols, size_t n_leaves, size_t
   uint64_t *D = digests;
   if (!D) {
     CP_TRY(ensure_scratch(ctx, n_trees * per_tree * sizeof(uint64_t)));
-    D = (uint64_t *)ctx->scratch;
+    D = ctx->scratch.get<uint64_t>();
   }
   const dim3 grid(blocks_for(n_leaves, merkle::THREADS), (unsigned)n_trees), block(merkle::THREADS);
   // a few thousand leaves: the launch is bound by the latency of one lane's chain of permutations — twelve lanes per leaf then
@@ -441,12 +433,11 @@ cp_ctx *cp_ctx_create(int device) try {
     set_error(nullptr, CP_ERR_INVALID_ARG, "device %d out of range (have %d)", device, n);
     return nullptr;
   }
-  cp_ctx *ctx = new (std::nothrow) cp_ctx();
+  cp_ctx *ctx = new (std::nothrow) cp_ctx(device);
   if (!ctx) {
     set_error(nullptr, CP_ERR_OOM, "out of host memory");
     return nullptr;
   }
-  ctx->device = device;
   auto fail = [&](const char *what, hipError_t e) {
     set_error(nullptr, CP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     delete ctx;
@@ -458,8 +449,7 @@ cp_ctx *cp_ctx_create(int device) try {
   if (e != hipSuccess) return fail("hipStreamCreate", e);
   if (upload_constants(ctx) != CP_OK || power_on_self_test(ctx) != CP_OK) {
     std::string msg = ctx->error;
-    hipStreamDestroy(ctx->stream);
-    delete ctx;
+    cp_ctx_destroy(ctx);
     g_tls_error = msg;
     return nullptr;
   }
@@ -478,20 +468,12 @@ void cp_ctx_destroy(cp_ctx *ctx) {
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   prof_flush(ctx);
   for (auto e : ctx->prof_pool) hipEventDestroy(e);
-  for (auto &kv : ctx->pow_tables) hipFree(kv.second.dev);
-  for (auto &kv : ctx->prescale_tables) hipFree(kv.second);
-  for (auto &kv : ctx->l0_tables) hipFree(kv.second);
-  for (auto &kv : ctx->air_sel_tables) hipFree(kv.second);
-  for (auto &ch : ctx->arena.chunks) hipFree(ch.first);
-  if (ctx->scratch) hipFree(ctx->scratch);
-  if (ctx->wires_stage) hipFree(ctx->wires_stage);
-  for (auto &kv : ctx->fr_twiddles) hipFree(kv.second);
-  if (ctx->fr_work) hipFree(ctx->fr_work);
-  for (auto &t : ctx->fr_pow)
-    if (t.tab) hipFree(t.tab);
-  if (ctx->msm_ws) hipFree(ctx->msm_ws);
-  if (ctx->pin) hipHostFree(ctx->pin);
-  if (ctx->noncanonical_flag) hipHostFree(ctx->noncanonical_flag);
+  // every owner of the context, between the synchronisation above and the destruction of the stream below (dev_mem.h, rule 2)
+  ctx->pow_tables.clear(); ctx->prescale_tables.clear(); ctx->l0_tables.clear(); ctx->air_sel_tables.clear(); ctx->fr_twiddles.clear();
+  ctx->arena.chunks.clear();
+  for (DevBuf *b : {&ctx->scratch, &ctx->wires_stage, &ctx->fr_work, &ctx->fr_pow[0].tab, &ctx->fr_pow[1].tab, &ctx->msm_ws}) b->reset();
+  ctx->pin.reset();
+  ctx->noncanonical_flag.reset();
   if (ctx->stream) hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -502,7 +484,7 @@ int cp_ctx_set_lanes(cp_ctx *ctx, int lanes) try {
   if (lanes < 1 || lanes > 8) return set_error(ctx, CP_ERR_INVALID_ARG, "lanes must be 1..8 (got %d)", lanes);
   while ((int)ctx->lanes.size() < lanes) {
     cp_ctx *lane = cp_ctx_create(ctx->device);
-    if (!lane) return set_error(ctx, CP_ERR_HIP, "lane context: %s", cp_last_error(nullptr));
+    if (!lane) return lane_error(ctx);
     lane->parent = ctx;
     lane->transcript_mode = ctx->transcript_mode;
     ctx->lanes.push_back(lane);
@@ -537,14 +519,16 @@ int cp_dev_alloc(cp_ctx *ctx, size_t bytes, void **out) try {
   if (!out) return set_error(ctx, CP_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   if (bytes == 0) return CP_OK;
-  HIP_TRY(ctx, dev_malloc(ctx->device, out, bytes));
+  DevBuf b = ctx->buf();
+  CP_TRY(alloc_status(ctx, b.alloc(bytes), bytes));
+  *out = b.release();  // the caller's from here on (cp_dev_free)
   return CP_OK;
 } CP_CATCH(ctx)
 int cp_dev_free(cp_ctx *ctx, void *ptr) try {
   CHECK_CTX(ctx);
   if (!ptr) return CP_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipFree(ptr));
+  HIP_TRY(ctx, abi_dev_free(ptr));
   return CP_OK;
 } CP_CATCH(ctx)
 int cp_host_alloc(cp_ctx *ctx, size_t bytes, void **out) try {
@@ -552,14 +536,16 @@ int cp_host_alloc(cp_ctx *ctx, size_t bytes, void **out) try {
   if (!out) return set_error(ctx, CP_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   if (bytes == 0) return CP_OK;
-  if (hipHostMalloc(out, bytes, hipHostMallocDefault) != hipSuccess) { *out = nullptr; return set_error(ctx, CP_ERR_OOM, "hipHostMalloc of %zu bytes failed", bytes); }
+  PinBuf b(pin_pool(), ctx->device);
+  CP_TRY(alloc_status(ctx, b.alloc(bytes), bytes));
+  *out = b.release();  // the caller's from here on (cp_host_free)
   return CP_OK;
 } CP_CATCH(ctx)
 int cp_host_free(cp_ctx *ctx, void *ptr) try {
   CHECK_CTX(ctx);
   if (!ptr) return CP_OK;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  HIP_TRY(ctx, hipHostFree(ptr));
+  HIP_TRY(ctx, abi_host_free(ptr));
   return CP_OK;
 } CP_CATCH(ctx)
 int cp_h2d(cp_ctx *ctx, void *dst, const void *src, size_t bytes) try {
@@ -583,20 +569,20 @@ __global__ __launch_bounds__(256) void k_flag_noncanonical(const uint64_t *__res
 // enqueue the scan of v[0, n) (device memory) on the context's stream; the flag accumulates over several calls until it is read
 int canonical_check_enqueue(cp_ctx *ctx, const uint64_t *v_dev, size_t n, bool reset) {
   if (!ctx->noncanonical_flag) {
-    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->noncanonical_flag, 64, hipHostMallocDefault));
-    *ctx->noncanonical_flag = 0;
+    CP_TRY(alloc_status(ctx, ctx->noncanonical_flag.alloc(64), 64));
+    *ctx->noncanonical_flag.get<uint32_t>() = 0;
   }
   if (reset) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // no earlier scan may still be writing
-    __atomic_store_n(ctx->noncanonical_flag, 0u, __ATOMIC_SEQ_CST);
+    __atomic_store_n(ctx->noncanonical_flag.get<uint32_t>(), 0u, __ATOMIC_SEQ_CST);
   }
   if (n == 0) return CP_OK;
   const size_t blocks = std::min<size_t>(blocks_for(n, 256), 4096);
-  LAUNCH(ctx, "canonical_check", k_flag_noncanonical, dim3((unsigned)blocks), dim3(256), v_dev, n, ctx->noncanonical_flag);
+  LAUNCH(ctx, "canonical_check", k_flag_noncanonical, dim3((unsigned)blocks), dim3(256), v_dev, n, ctx->noncanonical_flag.get<uint32_t>());
   return CP_OK;
 }
 // after the stream has been synchronised: did any scan since the last reset meet an element >= p?
-bool canonical_check_failed(cp_ctx *ctx) { return ctx->noncanonical_flag && __atomic_load_n(ctx->noncanonical_flag, __ATOMIC_SEQ_CST) != 0; }
+bool canonical_check_failed(cp_ctx *ctx) { return ctx->noncanonical_flag && __atomic_load_n(ctx->noncanonical_flag.get<uint32_t>(), __ATOMIC_SEQ_CST) != 0; }
 extern "C" {
 int cp_d2h(cp_ctx *ctx, void *dst, const void *src, size_t bytes) try {
   CHECK_CTX(ctx);
@@ -699,7 +685,7 @@ int cp_ntt_dev(cp_ctx *ctx, uint64_t *data, int log_n, size_t batch, size_t stri
   uint64_t *tmp = nullptr;
   if (need_tmp) {
     CP_TRY(ensure_scratch(ctx, batch * n * sizeof(uint64_t)));
-    tmp = (uint64_t *)ctx->scratch;
+    tmp = ctx->scratch.get<uint64_t>();
   }
   if (flags & CP_NTT_BITREV_IN) {  // un-permute the input first (v1: explicit pass)
     CP_TRY(bitrev_copy(ctx, data, tmp, stride, n, log_n, batch, nullptr));
@@ -734,14 +720,12 @@ int cp_ntt(cp_ctx *ctx, uint64_t *data_host, int log_n, size_t batch, unsigned f
   if (!data_host) return set_error(ctx, CP_ERR_INVALID_ARG, "data is NULL");
   if (log_n < 0 || log_n > 32) return set_error(ctx, CP_ERR_INVALID_ARG, "log_n %d out of range [0,32]", log_n);
   size_t n = (size_t)1 << log_n, bytes = batch * n * sizeof(uint64_t);
-  uint64_t *d = nullptr;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&d, bytes));
-  int rc = cp_h2d(ctx, d, data_host, bytes);
-  if (rc == CP_OK) rc = cp_ntt_dev(ctx, d, log_n, batch, n, flags, coset_shift);
-  if (rc == CP_OK) rc = cp_d2h(ctx, data_host, d, bytes);
-  hipStreamSynchronize(ctx->stream);
-  hipFree(d);
-  return rc;
+  DevBag tmp = ctx->bag();  // synchronises the stream before it frees
+  uint64_t *d;
+  CP_TRY(alloc_status(ctx, tmp.alloc(&d, bytes), bytes));
+  CP_TRY(cp_h2d(ctx, d, data_host, bytes));
+  CP_TRY(cp_ntt_dev(ctx, d, log_n, batch, n, flags, coset_shift));
+  return cp_d2h(ctx, data_host, d, bytes);
 } CP_CATCH(ctx)
 
 int cp_lde_dev(cp_ctx *ctx, const uint64_t *coeffs, size_t in_stride, int log_n, int rate_bits,
@@ -792,7 +776,7 @@ int cp_field_mul(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, ui
   if (count > ((size_t)1 << 28)) return set_error(ctx, CP_ERR_INVALID_ARG, "count too large");
   const size_t bytes = count * sizeof(uint64_t);
   CP_TRY(ensure_scratch(ctx, 3 * bytes));
-  uint64_t *a = (uint64_t *)ctx->scratch, *b = a + count, *o = b + count;
+  uint64_t *a = ctx->scratch.get<uint64_t>(), *b = a + count, *o = b + count;
   CP_TRY(cp_h2d(ctx, a, a_host, bytes));
   CP_TRY(cp_h2d(ctx, b, b_host, bytes));
   LAUNCH(ctx, "field_mul", k_field_mul, dim3(blocks_for(count, 256)), dim3(256), a, b, o, count);
@@ -816,9 +800,9 @@ int cp_poseidon_permute(cp_ctx *ctx, uint64_t *states_host, size_t count) try {
   if (!states_host) return set_error(ctx, CP_ERR_INVALID_ARG, "states is NULL");
   size_t bytes = count * 12 * sizeof(uint64_t);
   CP_TRY(ensure_scratch(ctx, bytes));
-  CP_TRY(cp_h2d(ctx, ctx->scratch, states_host, bytes));
-  CP_TRY(cp_poseidon_permute_dev(ctx, (uint64_t *)ctx->scratch, count));
-  return cp_d2h(ctx, states_host, ctx->scratch, bytes);
+  CP_TRY(cp_h2d(ctx, ctx->scratch.get(), states_host, bytes));
+  CP_TRY(cp_poseidon_permute_dev(ctx, ctx->scratch.get<uint64_t>(), count));
+  return cp_d2h(ctx, states_host, ctx->scratch.get(), bytes);
 } CP_CATCH(ctx)
 
 int cp_hash_no_pad(cp_ctx *ctx, const uint64_t *in_host, size_t count, size_t len,
@@ -830,7 +814,7 @@ int cp_hash_no_pad(cp_ctx *ctx, const uint64_t *in_host, size_t count, size_t le
   size_t in_bytes = count * len * sizeof(uint64_t), out_bytes = count * 32;
   size_t in_al = (in_bytes + 255) & ~(size_t)255;
   CP_TRY(ensure_scratch(ctx, in_al + out_bytes));
-  uint64_t *din = (uint64_t *)ctx->scratch, *dout = (uint64_t *)((char *)ctx->scratch + in_al);
+  uint64_t *din = ctx->scratch.get<uint64_t>(), *dout = (uint64_t *)(ctx->scratch.get<char>() + in_al);
   if (in_bytes) CP_TRY(cp_h2d(ctx, din, in_host, in_bytes));
   LAUNCH(ctx, "leaf_hash_rows", merkle::k_leaf_hash_rows, dim3(blocks_for(count, merkle::THREADS)),
          dim3(merkle::THREADS), din, count, (int)len, dout, 1);
@@ -844,7 +828,7 @@ int cp_two_to_one(cp_ctx *ctx, const uint64_t *left_host, const uint64_t *right_
   if (!left_host || !right_host || !out_host) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL pointer");
   size_t b = count * 32;
   CP_TRY(ensure_scratch(ctx, 3 * b));
-  uint64_t *l = (uint64_t *)ctx->scratch, *r = l + count * 4, *o = r + count * 4;
+  uint64_t *l = ctx->scratch.get<uint64_t>(), *r = l + count * 4, *o = r + count * 4;
   CP_TRY(cp_h2d(ctx, l, left_host, b));
   CP_TRY(cp_h2d(ctx, r, right_host, b));
   LAUNCH(ctx, "two_to_one", merkle::k_two_to_one, dim3(blocks_for(count, merkle::THREADS)),
@@ -878,25 +862,18 @@ int cp_merkle_cap(cp_ctx *ctx, const uint64_t *rows_host, size_t n_leaves, size_
   if (leaf_len == 0 || leaf_len > (1u << 20)) return set_error(ctx, CP_ERR_INVALID_ARG, "leaf_len %zu out of range", leaf_len);
   size_t cap_n = (size_t)1 << cap_height;
   size_t rows_bytes = n_leaves * leaf_len * sizeof(uint64_t);
-  uint64_t *rows = nullptr, *cap = nullptr;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&rows, rows_bytes));
-  hipError_t e = dev_malloc(ctx->device, (void **)&cap, cap_n * 32);
-  if (e != hipSuccess) { hipFree(rows); return set_error(ctx, CP_ERR_OOM, "hipMalloc: %s", hipGetErrorString(e)); }
-  int rc = cp_h2d(ctx, rows, rows_host, rows_bytes);
+  DevBag tmp = ctx->bag();  // synchronises the stream before it frees
+  uint64_t *rows, *cap;
+  CP_TRY(alloc_status(ctx, tmp.alloc(&rows, rows_bytes), rows_bytes));
+  CP_TRY(alloc_status(ctx, tmp.alloc(&cap, cap_n * 32), cap_n * 32));
+  CP_TRY(cp_h2d(ctx, rows, rows_host, rows_bytes));
   size_t per_tree = merkle_words_per_tree(n_leaves, cap_height);
-  if (rc == CP_OK) rc = ensure_scratch(ctx, per_tree * sizeof(uint64_t));
-  if (rc == CP_OK) {
-    uint64_t *level0 = (uint64_t *)ctx->scratch;
-    hipLaunchKernelGGL(merkle::k_leaf_hash_rows, dim3(blocks_for(n_leaves, merkle::THREADS)),
-                       dim3(merkle::THREADS), 0, ctx->stream, rows, n_leaves, (int)leaf_len, level0, 0);
-    if (hipGetLastError() != hipSuccess) rc = set_error(ctx, CP_ERR_HIP, "leaf hash launch failed");
-    if (rc == CP_OK) rc = merkle_levels(ctx, level0, per_tree, n_leaves, 1, cap_height, cap);
-  }
-  if (rc == CP_OK) rc = cp_d2h(ctx, cap_host, cap, cap_n * 32);
-  hipStreamSynchronize(ctx->stream);
-  hipFree(rows);
-  hipFree(cap);
-  return rc;
+  CP_TRY(ensure_scratch(ctx, per_tree * sizeof(uint64_t)));
+  uint64_t *level0 = ctx->scratch.get<uint64_t>();
+  LAUNCH(ctx, "leaf_hash_rows", merkle::k_leaf_hash_rows, dim3(blocks_for(n_leaves, merkle::THREADS)), dim3(merkle::THREADS), rows, n_leaves,
+         (int)leaf_len, level0, 0);
+  CP_TRY(merkle_levels(ctx, level0, per_tree, n_leaves, 1, cap_height, cap));
+  return cp_d2h(ctx, cap_host, cap, cap_n * 32);
 } CP_CATCH(ctx)
 
 // ---- commit ---------------------------------------------------------------------------------
@@ -913,32 +890,21 @@ int cp_commit_batch_dev(cp_ctx *ctx, const uint64_t *values, size_t k, size_t n_
   size_t n = (size_t)1 << log_n, N = n << rate_bits, polys = k * n_trees;
   if (!valid_merkle_shape(N, cap_height)) return set_error(ctx, CP_ERR_INVALID_ARG, "cap_height %d too large", cap_height);
   uint64_t *coeffs = coeffs_dev;
-  uint64_t *own = nullptr;
-  if (!coeffs) {
-    HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&own, polys * n * sizeof(uint64_t)));
-    coeffs = own;
-  }
-  int rc;
+  DevBag tmp = ctx->bag();  // holding something, it synchronises the stream before it frees
+  if (!coeffs) CP_TRY(alloc_status(ctx, tmp.alloc(&coeffs, polys * n * sizeof(uint64_t)), polys * n * sizeof(uint64_t)));
   if (log_n == ntt16::LOG_TILE) {
     // one launch: values -> natural-order coefficients (read from `values`, written to `coeffs`)
     DifExtra ex;
     ex.src = values;
     ex.src_stride = n;
     ex.natural_out = true;
-    rc = run_dif(ctx, coeffs, log_n, polys, n, true, gl::inv((uint64_t)n), nullptr, ex);
+    CP_TRY(run_dif(ctx, coeffs, log_n, polys, n, true, gl::inv((uint64_t)n), nullptr, ex));
   } else {
-    rc = cp_d2d(ctx, coeffs, values, polys * n * sizeof(uint64_t));
-    if (rc == CP_OK) rc = cp_ntt_dev(ctx, coeffs, log_n, polys, n, CP_NTT_INVERSE, 0);
+    CP_TRY(cp_d2d(ctx, coeffs, values, polys * n * sizeof(uint64_t)));
+    CP_TRY(cp_ntt_dev(ctx, coeffs, log_n, polys, n, CP_NTT_INVERSE, 0));
   }
-  if (rc == CP_OK)
-    rc = cp_lde_dev(ctx, coeffs, n, log_n, rate_bits, polys, 7, CP_NTT_BITREV_OUT, lde_dev, N);
-  if (rc == CP_OK)
-    rc = merkle_cols_batch(ctx, lde_dev, N, k, N, n_trees, k * N, cap_height, digests_dev, caps_dev);
-  if (own) {
-    hipStreamSynchronize(ctx->stream);
-    hipFree(own);
-  }
-  return rc;
+  CP_TRY(cp_lde_dev(ctx, coeffs, n, log_n, rate_bits, polys, 7, CP_NTT_BITREV_OUT, lde_dev, N));
+  return merkle_cols_batch(ctx, lde_dev, N, k, N, n_trees, k * N, cap_height, digests_dev, caps_dev);
 } CP_CATCH(ctx)
 
 int cp_commit_dev(cp_ctx *ctx, const uint64_t *values, size_t k, int log_n, int rate_bits,

@@ -24,20 +24,59 @@
 #include "gl.h"
 #include "host_util.h"
 #include "dev_pool.h"
+#include "dev_mem.h"
 
 inline thread_local std::string g_tls_error = "";
+inline thread_local int g_tls_status = CP_OK;  // the code of this thread's last set_error: the status of a call that returns a handle
 
-namespace {
-
-struct PowTable {
-  uint64_t *dev = nullptr;  // 3 x 2048
+// ---- device buffer pool of the batch handles: dev_pool.h on hipMalloc / hipFree; one table for the whole library (inline:
+// shared by the translation units), sized by the number of visible devices
+struct HipRaw {
+  static constexpr int OOM = (int)hipErrorOutOfMemory;
+  static int malloc(void **p, size_t bytes) {
+    if (hostu::fault_fires(3)) return OOM;  // cp_fault_inject(CP_FAULT_DEVMEM): the runtime "has no memory left" once
+    hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return (int)e;
+  }
+  static void free(void *p) { (void)hipFree(p); }
 };
-
-}  // namespace
+inline DevPoolT<HipRaw> &dev_pool() {
+  static DevPoolT<HipRaw> pool(
+      [] { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); n = 0; } return (size_t)(n > 0 ? n : 0); }(),
+      (getenv("CITYPROVER_BATCH_POOL_MB") ? strtoull(getenv("CITYPROVER_BATCH_POOL_MB"), nullptr, 10) : 4096ull) << 20);
+  return pool;
+}
+// page-locked host memory through the same owner: a pool with no device table hands every request to its raw policy
+struct PinRaw {
+  static constexpr int OOM = (int)hipErrorOutOfMemory;
+  static int malloc(void **p, size_t bytes) {
+    hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return (int)e;
+  }
+  static void free(void *p) { (void)hipHostFree(p); }
+};
+inline DevPoolT<PinRaw> &pin_pool() {
+  static DevPoolT<PinRaw> pool(0, 0);
+  return pool;
+}
+// dev_mem.h on the two: every allocation of the library has one of these owners (the caller has made the device current)
+using DevBuf = DevBufT<DevPoolT<HipRaw>>;
+using DevBag = DevBagT<DevPoolT<HipRaw>>;
+using PinBuf = DevBufT<DevPoolT<PinRaw>>;
+// pointers that crossed the ABI (cp_dev_alloc / cp_host_alloc) come back raw, and the status goes to the caller
+inline hipError_t abi_dev_free(void *p) { return hipFree(p); }
+inline hipError_t abi_host_free(void *p) { return hipHostFree(p); }
 
 struct cp_ctx {
-  int device = -1;
+  explicit cp_ctx(int dev) : device(dev) {}
+  const int device;
   hipStream_t stream = nullptr;
+  // the stream-idle rule of dev_mem.h: asked before a buffer that queued work may use is given back
+  DevBuf::Idle stream_idle = [this] { return hipStreamSynchronize(stream) == hipSuccess; };
+  DevBuf buf(DevOwn own = DevOwn::RUNTIME) { return DevBuf(dev_pool(), device, own, stream_idle); }  // an empty owner on this context
+  DevBag bag(DevOwn own = DevOwn::RUNTIME) { return DevBag(dev_pool(), device, own, stream_idle); }  // the temporaries of one call
   std::string error;
   // cp_ctx_set_lanes: child contexts (own stream, arena, staging) among which ONE cp_prove_batch_host call is split, so
   // that a single-threaded caller gets the overlap of host phases and small kernels that several contexts give
@@ -45,42 +84,37 @@ struct cp_ctx {
   std::vector<cp_ctx *> lanes;
   int n_lanes = 1;
   int transcript_mode = -1;  // cp_ctx_set_device_transcript: -1 automatic (by batch size), 0 host, 1 device
-  std::map<uint64_t, PowTable> pow_tables;  // keyed by base
+  std::map<uint64_t, DevBuf> pow_tables;  // keyed by base: 3 x 2048
   struct PreKey { int log_n, rate_bits; uint64_t shift; bool operator<(const PreKey &o) const {
     return std::tie(log_n, rate_bits, shift) < std::tie(o.log_n, o.rate_bits, o.shift); } };
-  std::map<PreKey, uint64_t *> prescale_tables;  // LDE pre-scale tables [2^rate_bits][n]
-  std::map<std::pair<int, int>, uint64_t *> l0_tables;  // (degree_bits, rate_bits) -> L_0 on the LDE coset [N], storage order (get_l0_table)
-  std::map<std::pair<int, int>, uint64_t *> air_sel_tables;  // (degree_bits, q) -> z_last, L_0, L_(n-1) on the quotient coset [3][M] (stark.inc)
+  std::map<PreKey, DevBuf> prescale_tables;  // LDE pre-scale tables [2^rate_bits][n]
+  std::map<std::pair<int, int>, DevBuf> l0_tables;  // (degree_bits, rate_bits) -> L_0 on the LDE coset [N], storage order (get_l0_table)
+  std::map<std::pair<int, int>, DevBuf> air_sel_tables;  // (degree_bits, q) -> z_last, L_0, L_(n-1) on the quotient coset [3][M] (stark.inc)
   size_t lds_per_block = 0;  // the device's shared memory per workgroup, bytes (hipDeviceAttributeMaxSharedMemoryPerBlock; asked once)
   // scratch buffer reused by natural-order NTT epilogues / merkle host paths
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf scratch = buf();
   // page-locked host staging for the small transfers of a proving call (caps, challenges, openings, query words):
   // pageable copies block inside the runtime and serialise the contexts of a process
-  char *pin = nullptr;
-  size_t pin_bytes = 0, pin_off = 0;
+  PinBuf pin{pin_pool(), device};  // no idle callback: pin_reserve drains the stream itself before it grows
+  size_t pin_off = 0;
   // device-to-host copies that have been enqueued into the staging area and not yet handed to their destinations: a proving
   // call enqueues every output (caps, openings, query words, ...) behind its last kernel and synchronises ONCE (fetch_flush)
   struct PendingFetch { void *host; const char *stage; size_t bytes; };
   std::vector<PendingFetch> pending_fetches;
   // BLS12-381 F_r twiddle tables (fr_ntt.inc), keyed by (log_n, inverse)
-  std::map<std::pair<int, int>, void *> fr_twiddles;
-  void *fr_work = nullptr;  // grow-only work array of the F_r NTT
-  size_t fr_work_bytes = 0;
+  std::map<std::pair<int, int>, DevBuf> fr_twiddles;
+  DevBuf fr_work = buf();  // grow-only work array of the F_r NTT
   struct FrPowers {         // cached coset power table s^i, i < 2^log_n (Groth16 always asks for the same two)
-    void *tab = nullptr;
-    size_t bytes = 0;
+    DevBuf tab;
     int log_n = -1;
     uint64_t shift[4] = {0, 0, 0, 0};
-  } fr_pow[2];              // [0]: forward (powers of the shift), [1]: inverse (powers of its inverse)
-  void *msm_ws = nullptr;  // grow-only workspace of the MSMs (counts, sorted indices, buckets)
-  size_t msm_ws_bytes = 0;
+  } fr_pow[2] = {{buf()}, {buf()}};  // [0]: forward (powers of the shift), [1]: inverse (powers of its inverse)
+  DevBuf msm_ws = buf();  // grow-only workspace of the MSMs (counts, sorted indices, buckets)
   // device staging buffer for wire matrices that arrive in host memory (cp_prove / cp_prove_batch_host)
-  uint64_t *wires_stage = nullptr;
-  size_t wires_stage_bytes = 0;
+  DevBuf wires_stage = buf();
   // per-proof workspace arena (prover_tail.inc): chunks survive between proofs
   struct Arena {
-    std::vector<std::pair<char *, size_t>> chunks;
+    std::vector<DevBuf> chunks;
     size_t cur = 0, off = 0, used = 0;
   } arena;
   // optional per-kernel hipEvent timing (cp_profile_begin / cp_profile_end)
@@ -99,7 +133,7 @@ struct cp_ctx {
   std::vector<struct cp_poly_batch *> live_batches;
   // page-locked word a kernel sets when it meets a field element >= p in an array that came from the host (canonical_check_*
   // in cityprover.hip): the scan runs on the device behind the upload instead of on one host core in front of it
-  uint32_t *noncanonical_flag = nullptr;
+  PinBuf noncanonical_flag{pin_pool(), device};
   // cp_ctx_set_option: per-context values of the measurement switches (a lane asks its parent); empty = the process-wide
   // CITYPROVER_<NAME> environment variable, else the built-in default
   std::vector<std::pair<std::string, long>> options;
@@ -129,29 +163,6 @@ inline const char *const *knob_names() {
   return names;
 }
 
-// ---- device buffer pool of the batch handles: dev_pool.h on hipMalloc / hipFree; one table for the whole library (inline:
-// shared by the translation units), sized by the number of visible devices
-struct HipRaw {
-  static constexpr int OOM = (int)hipErrorOutOfMemory;
-  static int malloc(void **p, size_t bytes) {
-    if (hostu::fault_fires(3)) return OOM;  // cp_fault_inject(CP_FAULT_DEVMEM): the runtime "has no memory left" once
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return (int)e;
-  }
-  static void free(void *p) { (void)hipFree(p); }
-};
-inline DevPoolT<HipRaw> &dev_pool() {
-  static DevPoolT<HipRaw> pool(
-      [] { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); n = 0; } return (size_t)(n > 0 ? n : 0); }(),
-      (getenv("CITYPROVER_BATCH_POOL_MB") ? strtoull(getenv("CITYPROVER_BATCH_POOL_MB"), nullptr, 10) : 4096ull) << 20);
-  return pool;
-}
-// hipMalloc for every allocation of the library (the caller has made `device` current)
-inline hipError_t dev_malloc(int device, void **p, size_t bytes) { return (hipError_t)dev_pool().malloc(device, p, bytes); }
-inline hipError_t batch_pool_alloc(int device, void **p, size_t bytes) { return (hipError_t)dev_pool().alloc(device, p, bytes); }
-inline void batch_pool_free(int device, void *p, size_t bytes, bool reusable) { dev_pool().release(device, p, bytes, reusable); }
-
 namespace {
 
 int set_error(cp_ctx *ctx, int code, const char *fmt, ...) noexcept {
@@ -160,6 +171,7 @@ int set_error(cp_ctx *ctx, int code, const char *fmt, ...) noexcept {
   va_start(ap, fmt);
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
+  g_tls_status = code;
   try {  // the message is best effort: the status code is what must get out
     g_tls_error = buf;
     if (ctx) ctx->error = buf;
@@ -209,18 +221,16 @@ inline unsigned blocks_for(size_t n, unsigned threads) { return (unsigned)((n + 
                        hipGetErrorString(e__));                                 \
   } while (0)
 
-int ensure_scratch(cp_ctx *ctx, size_t bytes) {
-  if (ctx->scratch_bytes >= bytes) return CP_OK;
-  if (ctx->scratch) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(ctx->scratch));
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-  }
-  HIP_TRY(ctx, dev_malloc(ctx->device, &ctx->scratch, bytes));
-  ctx->scratch_bytes = bytes;
-  return CP_OK;
+// The status of an allocation (the int a DevBuf / DevBag / PinBuf call returns): out of memory is CP_ERR_OOM, anything else
+// CP_ERR_HIP - the HIP_TRY mapping, with the size in the message.
+int alloc_status(cp_ctx *ctx, int e, size_t bytes) {
+  if (e == (int)hipSuccess) return CP_OK;
+  return set_error(ctx, e == (int)hipErrorOutOfMemory ? CP_ERR_OOM : CP_ERR_HIP, "memory allocation of %zu bytes failed: %s", bytes,
+                   hipGetErrorString((hipError_t)e));
 }
+// cp_ctx_create refused a lane (child context): its message, and out of memory stays out of memory
+int lane_error(cp_ctx *ctx) { return set_error(ctx, g_tls_status == CP_ERR_OOM ? CP_ERR_OOM : CP_ERR_HIP, "lane context: %s", g_tls_error.c_str()); }
+int ensure_scratch(cp_ctx *ctx, size_t bytes) { return alloc_status(ctx, ctx->scratch.grow(bytes), bytes); }
 
 hipEvent_t prof_event(cp_ctx *ctx) {
   if (!ctx->prof_pool.empty()) {

@@ -53,6 +53,8 @@ class DevPoolT {
     return e;
   }
 
+  static void free(void *p) { Raw::free(p); }  // what `malloc` handed out and no pool ever held
+
   // a buffer of exactly `bytes`: from the pool when it holds one, else from the runtime
   int alloc(int device, void **p, size_t bytes) {
     if (has_pool(device)) {

@@ -1,34 +1,19 @@
-// Host side of the F_r NTT (kernels: fr_ntt.h). Included by cityprover.hip after msm.inc (DevTemps).
+// Host side of the F_r NTT (kernels: fr_ntt.h). Included by bls.hip after msm.inc.
 namespace {
 
 // twiddle table omega^i, i < n/2 (omega = the primitive n-th root, or its inverse), cached per context
 int fr_twiddles(cp_ctx *ctx, int log_n, bool inverse, const blsfr::Fr **out) {
   const auto key = std::make_pair(log_n, inverse ? 1 : 0);
   auto it = ctx->fr_twiddles.find(key);
-  if (it != ctx->fr_twiddles.end()) { *out = (const blsfr::Fr *)it->second; return CP_OK; }
+  if (it != ctx->fr_twiddles.end()) { *out = it->second.get<const blsfr::Fr>(); return CP_OK; }
   const size_t half = log_n ? ((size_t)1 << (log_n - 1)) : 1;
-  blsfr::Fr *tab = nullptr;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&tab, half * sizeof(blsfr::Fr)));
+  DevBuf tab = ctx->buf();
+  CP_TRY(alloc_status(ctx, tab.alloc(half * sizeof(blsfr::Fr)), half * sizeof(blsfr::Fr)));
   blsfr::Fr w = blsfr::fr_from_canonical(BLS_FR_ROOTS[log_n]);
   if (inverse) w = blsfr::fr_inv(w);
-  hipLaunchKernelGGL(frntt::k_powers, dim3(blocks_for(half, 256)), dim3(256), 0, ctx->stream, w, half, tab);
-  if (hipGetLastError() != hipSuccess) { (void)hipFree(tab); return set_error(ctx, CP_ERR_HIP, "twiddle table launch failed"); }
-  ctx->fr_twiddles[key] = tab;
-  *out = tab;
-  return CP_OK;
-}
-
-// grow-only device buffer owned by the context (no hipMalloc / hipFree in the steady state)
-int fr_buffer(cp_ctx *ctx, void **buf, size_t *have, size_t need, void **out) {
-  if (*have < need) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    if (dev_malloc(ctx->device, buf, need) != hipSuccess) return set_error(ctx, CP_ERR_OOM, "hipMalloc of %zu bytes failed", need);
-    *have = need;
-  }
-  *out = *buf;
+  LAUNCH(ctx, "fr_twiddles", frntt::k_powers, dim3(blocks_for(half, 256)), dim3(256), w, half, tab.get<blsfr::Fr>());
+  *out = tab.get<const blsfr::Fr>();
+  ctx->fr_twiddles[key] = std::move(tab);
   return CP_OK;
 }
 
@@ -38,8 +23,9 @@ int fr_ntt_run(cp_ctx *ctx, uint64_t *data_dev, int log_n, unsigned flags, const
   const bool inverse = flags & CP_NTT_INVERSE, coset = flags & CP_NTT_COSET;
   if (coset && !shift) return set_error(ctx, CP_ERR_INVALID_ARG, "coset transform without a shift");
   const size_t n = (size_t)1 << log_n;
-  blsfr::Fr *work, *powers = nullptr;
-  CP_TRY(fr_buffer(ctx, &ctx->fr_work, &ctx->fr_work_bytes, n * sizeof(blsfr::Fr), (void **)&work));
+  blsfr::Fr *powers = nullptr;
+  CP_TRY(alloc_status(ctx, ctx->fr_work.grow(n * sizeof(blsfr::Fr)), n * sizeof(blsfr::Fr)));  // grow-only: no hipMalloc / hipFree in the steady state
+  blsfr::Fr *work = ctx->fr_work.get<blsfr::Fr>();
   const blsfr::Fr *tw = nullptr;
   if (log_n > 0) CP_TRY(fr_twiddles(ctx, log_n, inverse, &tw));
   if (coset) {
@@ -55,12 +41,12 @@ int fr_ntt_run(cp_ctx *ctx, uint64_t *data_dev, int log_n, unsigned flags, const
     const bool hit = cache.tab && cache.log_n == log_n && memcmp(cache.shift, shift, 32) == 0;
     if (!hit) {
       cache.log_n = -1;
-      CP_TRY(fr_buffer(ctx, &cache.tab, &cache.bytes, n * sizeof(blsfr::Fr), (void **)&powers));
-      LAUNCH(ctx, "fr_powers", frntt::k_powers, dim3(blocks_for(n, 256)), dim3(256), s, n, powers);
+      CP_TRY(alloc_status(ctx, cache.tab.grow(n * sizeof(blsfr::Fr)), n * sizeof(blsfr::Fr)));
+      LAUNCH(ctx, "fr_powers", frntt::k_powers, dim3(blocks_for(n, 256)), dim3(256), s, n, cache.tab.get<blsfr::Fr>());
       cache.log_n = log_n;
       memcpy(cache.shift, shift, 32);
     }
-    powers = (blsfr::Fr *)cache.tab;
+    powers = cache.tab.get<blsfr::Fr>();
   }
   const blsfr::Fr *in_pow = coset && !inverse ? powers : nullptr;
   frntt::StoreArgs sa;
@@ -137,10 +123,10 @@ int cp_groth16_quotient_bls12381(cp_ctx *ctx, uint64_t *a_host, const uint64_t *
     for (size_t i = 0; i < n; i++)
       if (!blsfr::fr_is_canonical((const uint32_t *)(in[k] + 4 * i)))
         return set_error(ctx, CP_ERR_INVALID_ARG, "%c[%zu] is not canonical (>= r)", "abc"[k], i);
-  DevTemps D;
+  DevBag D = ctx->bag();
   uint64_t *d[3];
   for (int k = 0; k < 3; k++) {
-    CP_TRY(D.alloc(ctx, n * 32, (void **)&d[k]));
+    CP_TRY(alloc_status(ctx, D.alloc(&d[k], n * 32), n * 32));
     HIP_TRY(ctx, hipMemcpyAsync(d[k], in[k], n * 32, hipMemcpyHostToDevice, ctx->stream));
   }
   CP_TRY(groth16_quotient_run(ctx, d[0], d[1], d[2], log_n));
@@ -162,9 +148,9 @@ int cp_ntt_bls12381_fr(cp_ctx *ctx, uint64_t *data_host, int log_n, unsigned fla
   const size_t n = (size_t)1 << log_n;
   for (size_t i = 0; i < n; i++)
     if (!blsfr::fr_is_canonical((const uint32_t *)(data_host + 4 * i))) return set_error(ctx, CP_ERR_INVALID_ARG, "element %zu is not canonical (>= r)", i);
-  DevTemps D;
+  DevBag D = ctx->bag();
   uint64_t *d;
-  CP_TRY(D.alloc(ctx, n * 32, (void **)&d));
+  CP_TRY(alloc_status(ctx, D.alloc(&d, n * 32), n * 32));
   HIP_TRY(ctx, hipMemcpyAsync(d, data_host, n * 32, hipMemcpyHostToDevice, ctx->stream));
   CP_TRY(fr_ntt_run(ctx, d, log_n, flags, coset_shift));
   HIP_TRY(ctx, hipMemcpyAsync(data_host, d, n * 32, hipMemcpyDeviceToHost, ctx->stream));

@@ -7,33 +7,26 @@
 struct cp_poly_batch {
   cp_ctx *ctx = nullptr;  // nullptr once the context has been destroyed (orphan: cp_batch_destroy is the only call left)
   int device = 0;         // where the buffers live
-  bool exported = false;  // cp_batch_device_ptrs was called: the caller's streams may use the buffers (see core.h BatchPool)
   size_t k = 0;
   int degree_bits = 0, rate_bits = 0, cap_height = 0, n_salt = 0;
+  // pool-owned (dev_mem.h), behind the plain pointers below. A buffer goes back to the pool as reusable only when it was
+  // marked idle (cp_batch_destroy, after the stream was drained) or when the whole device has been waited for (a commit
+  // that failed half way); cp_batch_device_ptrs marks all five exported: the caller's streams may use them (dev_pool.h)
+  DevBuf own[5];
   uint64_t *coeffs = nullptr, *lde = nullptr, *digests = nullptr, *cap = nullptr, *salt = nullptr;
   std::vector<uint64_t> cap_host;
 };
 
 namespace {
 
-// the pool itself: core.h (BatchPool, batch_pool_alloc / batch_pool_free / batch_pool_trim, dev_malloc)
+// the pool itself: dev_pool.h, instantiated in core.h (dev_pool()); the owners: dev_mem.h
 
-size_t batch_bytes_coeffs(const cp_poly_batch *b) { return b->k * ((size_t)8 << b->degree_bits); }
-size_t batch_bytes_lde(const cp_poly_batch *b) { return b->k * ((size_t)8 << (b->degree_bits + b->rate_bits)); }
-size_t batch_bytes_digests(const cp_poly_batch *b) { return merkle_words_per_tree((size_t)1 << (b->degree_bits + b->rate_bits), b->cap_height) * 8; }
-size_t batch_bytes_cap(const cp_poly_batch *b) { return ((size_t)4 << b->cap_height) * 8; }
-size_t batch_bytes_salt(const cp_poly_batch *b) { return (size_t)CP_SALT_SIZE * ((size_t)8 << (b->degree_bits + b->rate_bits)); }
-
-// the caller has made sure that the library's own stream holds no work on the buffers
-void poly_batch_free(cp_poly_batch *b) {
-  if (!b) return;
-  const bool reusable = !b->exported;
-  batch_pool_free(b->device, b->coeffs, batch_bytes_coeffs(b), reusable);
-  batch_pool_free(b->device, b->lde, batch_bytes_lde(b), reusable);
-  batch_pool_free(b->device, b->digests, batch_bytes_digests(b), reusable);
-  batch_pool_free(b->device, b->cap, batch_bytes_cap(b), reusable);
-  batch_pool_free(b->device, b->salt, batch_bytes_salt(b), reusable);
-  delete b;
+// one buffer of the handle, from the pool
+int batch_buf(cp_ctx *ctx, cp_poly_batch *b, int i, size_t bytes, uint64_t **out) {
+  b->own[i] = DevBuf(dev_pool(), b->device, DevOwn::POOLED, [] { return hipDeviceSynchronize() == hipSuccess; });
+  CP_TRY(alloc_status(ctx, b->own[i].alloc(bytes), bytes));
+  *out = b->own[i].get<uint64_t>();
+  return CP_OK;
 }
 void batch_register(cp_ctx *ctx, cp_poly_batch *b) {
   std::lock_guard<std::mutex> l(ctx->batches_m);
@@ -86,17 +79,17 @@ int poly_batch_commit(cp_ctx *ctx, const uint64_t *src, bool from_dev, size_t k,
   if (db < 0 || rb < 0 || db + rb > 30 || db + rb < 1) return set_error(ctx, CP_ERR_INVALID_ARG, "degree_bits / rate_bits out of range");
   const size_t n = (size_t)1 << db, N = n << rb;
   if (!valid_merkle_shape(N, ch)) return set_error(ctx, CP_ERR_INVALID_ARG, "cap_height %d out of range for 2^%d leaves", ch, db + rb);
-  cp_poly_batch *b = new (std::nothrow) cp_poly_batch();
+  std::unique_ptr<cp_poly_batch> guard(new (std::nothrow) cp_poly_batch());  // dropped on a failure: the owners wait for the device
+  cp_poly_batch *b = guard.get();
   if (!b) return set_error(ctx, CP_ERR_OOM, "out of host memory");
-  struct Guard { cp_poly_batch *b; ~Guard() { if (b) { (void)hipDeviceSynchronize(); poly_batch_free(b); } } } guard{b};
   b->ctx = ctx; b->device = ctx->device; b->k = k; b->degree_bits = db; b->rate_bits = rb; b->cap_height = ch;
-  HIP_TRY(ctx, batch_pool_alloc(b->device, (void **)&b->coeffs, batch_bytes_coeffs(b)));
-  HIP_TRY(ctx, batch_pool_alloc(b->device, (void **)&b->lde, batch_bytes_lde(b)));
-  HIP_TRY(ctx, batch_pool_alloc(b->device, (void **)&b->digests, batch_bytes_digests(b)));
-  HIP_TRY(ctx, batch_pool_alloc(b->device, (void **)&b->cap, batch_bytes_cap(b)));
+  CP_TRY(batch_buf(ctx, b, 0, b->k * ((size_t)8 << db), &b->coeffs));
+  CP_TRY(batch_buf(ctx, b, 1, b->k * N * 8, &b->lde));
+  CP_TRY(batch_buf(ctx, b, 2, merkle_words_per_tree(N, ch) * 8, &b->digests));
+  CP_TRY(batch_buf(ctx, b, 3, ((size_t)4 << ch) * 8, &b->cap));
   if (salts) {
     b->n_salt = CP_SALT_SIZE;
-    HIP_TRY(ctx, batch_pool_alloc(b->device, (void **)&b->salt, batch_bytes_salt(b)));
+    CP_TRY(batch_buf(ctx, b, 4, (size_t)CP_SALT_SIZE * N * 8, &b->salt));
     if (from_dev) CP_TRY(cp_d2d(ctx, b->salt, salts, (size_t)CP_SALT_SIZE * N * 8));
     else CP_TRY(cp_h2d(ctx, b->salt, salts, (size_t)CP_SALT_SIZE * N * 8));
   }
@@ -121,9 +114,8 @@ int poly_batch_commit(cp_ctx *ctx, const uint64_t *src, bool from_dev, size_t k,
   }
   for (uint64_t v : b->cap_host)
     if (v >= gl::P) return set_error(ctx, CP_ERR_INTERNAL, "non-canonical cap element");
-  guard.b = nullptr;
   batch_register(ctx, b);
-  *out = b;
+  *out = guard.release();
   return CP_OK;
 }
 
@@ -183,7 +175,8 @@ void cp_batch_destroy(cp_poly_batch *b) {
     (void)hipStreamSynchronize(b->ctx->stream);
     batch_unregister(b->ctx, b);
   }
-  poly_batch_free(b);
+  for (DevBuf &o : b->own) o.mark_idle();  // exported ones stay exported
+  delete b;
 }
 
 int cp_batch_pool_stats(int device, cp_batch_pool_info *out) try {
@@ -221,7 +214,7 @@ int cp_batch_cap(cp_poly_batch *b, uint64_t *cap_out) try {
 
 int cp_batch_device_ptrs(cp_poly_batch *b, const uint64_t **coeffs_dev_out, const uint64_t **lde_dev_out) try {
   CHECK_BATCH(b);
-  b->exported = true;
+  for (DevBuf &o : b->own) o.mark_exported();
   if (coeffs_dev_out) *coeffs_dev_out = b->coeffs;
   if (lde_dev_out) *lde_dev_out = b->lde;
   return CP_OK;

@@ -62,7 +62,7 @@ extern "C" int cp_groth16_prove_bls12381(cp_ctx *ctx, const cp_groth16_pk *pk, c
   J2 sb2;
   if (ctx->lanes.empty() && !ctx->parent) {
     cp_ctx *lane = cp_ctx_create(ctx->device);
-    if (!lane) return set_error(ctx, CP_ERR_HIP, "lane context: %s", cp_last_error(nullptr));
+    if (!lane) return lane_error(ctx);
     lane->parent = ctx;
     ctx->lanes.push_back(lane);
   }

@@ -5,31 +5,14 @@ namespace {
 static_assert(sizeof(bls::Affine) == CP_G1_AFFINE_BYTES, "CP_G1_AFFINE_BYTES out of date");
 static_assert(sizeof(bls::Affine2) == CP_G2_AFFINE_BYTES, "CP_G2_AFFINE_BYTES out of date");
 
-struct DevTemps {  // device copies of host inputs: freed when the call ends, on every path
-  std::vector<void *> ptrs;
-  ~DevTemps() { for (void *p : ptrs) (void)hipFree(p); }
-  int alloc(cp_ctx *ctx, size_t bytes, void **out) {
-    *out = nullptr;
-    if (dev_malloc(ctx->device, out, bytes ? bytes : 1) != hipSuccess) return set_error(ctx, CP_ERR_OOM, "hipMalloc of %zu bytes failed", bytes);
-    ptrs.push_back(*out);
-    return CP_OK;
-  }
-};
 struct DevBufs {  // carves the context's grow-only MSM workspace: plan() every array, commit(), then take() in the same order
   size_t need = 0, at = 0;
   char *base = nullptr;
   static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
   void plan(size_t bytes) { need += pad(bytes); }
   int commit(cp_ctx *ctx) {
-    if (need > ctx->msm_ws_bytes) {
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      if (ctx->msm_ws) (void)hipFree(ctx->msm_ws);
-      ctx->msm_ws = nullptr;
-      ctx->msm_ws_bytes = 0;
-      if (dev_malloc(ctx->device, &ctx->msm_ws, need) != hipSuccess) return set_error(ctx, CP_ERR_OOM, "hipMalloc of %zu bytes failed", need);
-      ctx->msm_ws_bytes = need;
-    }
-    base = (char *)ctx->msm_ws;
+    CP_TRY(alloc_status(ctx, ctx->msm_ws.grow(need), need));
+    base = ctx->msm_ws.get<char>();
     return CP_OK;
   }
   template <class T>
@@ -187,17 +170,17 @@ int msm_host(cp_ctx *ctx, const uint64_t *scalars_host, const uint64_t *points_x
       for (size_t h = 0; h < PW / 12; h++)
         if (!canonical_words(w + 12 * h)) return set_error(ctx, CP_ERR_INVALID_ARG, "point %zu: coordinate is not canonical (>= p)", i);
     }
-    DevTemps D;
+    DevBag D = ctx->bag();  // device copies of the host inputs: freed when the call ends, on every path
     uint64_t *d_s, *d_xy;
     bls::AffineT<F> *d_m;
     uint8_t *d_inf = nullptr;
-    CP_TRY(D.alloc(ctx, n * 32, (void **)&d_s));
-    CP_TRY(D.alloc(ctx, n * PW * 4, (void **)&d_xy));
-    CP_TRY(D.alloc(ctx, n * sizeof(bls::AffineT<F>), (void **)&d_m));
+    CP_TRY(alloc_status(ctx, D.alloc(&d_s, n * 32), n * 32));
+    CP_TRY(alloc_status(ctx, D.alloc(&d_xy, n * PW * 4), n * PW * 4));
+    CP_TRY(alloc_status(ctx, D.alloc(&d_m, n * sizeof(bls::AffineT<F>)), n * sizeof(bls::AffineT<F>)));
     HIP_TRY(ctx, hipMemcpyAsync(d_s, scalars_host, n * 32, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_xy, points_xy_host, n * PW * 4, hipMemcpyHostToDevice, ctx->stream));
     if (points_inf_host) {
-      CP_TRY(D.alloc(ctx, n, (void **)&d_inf));
+      CP_TRY(alloc_status(ctx, D.alloc(&d_inf, n), n));
       HIP_TRY(ctx, hipMemcpyAsync(d_inf, points_inf_host, n, hipMemcpyHostToDevice, ctx->stream));
     }
     CP_TRY(msm_prepare_dev<F>(ctx, d_xy, n, d_m));

@@ -70,8 +70,8 @@ int arena_alloc(cp_ctx *ctx, size_t bytes, void **out) {
   bytes = (bytes + 255) & ~(size_t)255;
   auto &A = ctx->arena;
   while (A.cur < A.chunks.size()) {
-    if (A.off + bytes <= A.chunks[A.cur].second) {
-      *out = A.chunks[A.cur].first + A.off;
+    if (A.off + bytes <= A.chunks[A.cur].bytes()) {
+      *out = A.chunks[A.cur].get<char>() + A.off;
       A.off += bytes;
       A.used += bytes;
       return CP_OK;
@@ -80,13 +80,14 @@ int arena_alloc(cp_ctx *ctx, size_t bytes, void **out) {
     A.off = 0;
   }
   size_t sz = bytes > ((size_t)64 << 20) ? bytes : ((size_t)64 << 20);
-  char *p = nullptr;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&p, sz));
-  A.chunks.push_back({p, sz});
+  A.chunks.reserve(A.chunks.size() + 1);
+  DevBuf chunk = ctx->buf();
+  CP_TRY(alloc_status(ctx, chunk.alloc(sz), sz));
+  *out = chunk.get();
+  A.chunks.push_back(std::move(chunk));
   A.cur = A.chunks.size() - 1;
   A.off = bytes;
   A.used += bytes;
-  *out = p;
   return CP_OK;
 }
 // called with the stream idle: rewind; if the call spilled over several chunks, coalesce them into one
@@ -94,30 +95,23 @@ void arena_reset(cp_ctx *ctx) {
   auto &A = ctx->arena;
   if (A.chunks.size() > 1) {
     size_t total = 0;
-    for (auto &c : A.chunks) { total += c.second; (void)hipFree(c.first); }
-    A.chunks.clear();
-    char *p = nullptr;
-    if (dev_malloc(ctx->device, (void **)&p, total) == hipSuccess) A.chunks.push_back({p, total});
+    for (auto &c : A.chunks) total += c.bytes();
+    A.chunks.resize(1);  // frees the others first
+    if (A.chunks[0].alloc(total) != 0) A.chunks.clear();  // refused: the arena is empty and grows again
   }
   A.cur = 0;
   A.off = 0;
   A.used = 0;
 }
 
-int batch_alloc_persistent(cp_ctx *ctx, DevBatch &b, size_t k, size_t n, size_t N, int cap_height) {
+// the arrays of `b` live in `mem` (the handle that holds b), not in the arena
+int batch_alloc_persistent(cp_ctx *ctx, DevBag &mem, DevBatch &b, size_t k, size_t n, size_t N, int cap_height) {
   b.k = k;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&b.coeffs, k * n * 8));
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&b.lde, k * N * 8));
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&b.digests, merkle_words_per_tree(N, cap_height) * 8));
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&b.cap, ((size_t)4 << cap_height) * 8));
-  return CP_OK;
-}
-void batch_free_persistent(DevBatch &b) {
-  if (b.coeffs) (void)hipFree(b.coeffs);
-  if (b.lde) (void)hipFree(b.lde);
-  if (b.digests) (void)hipFree(b.digests);
-  if (b.cap) (void)hipFree(b.cap);
-  b = DevBatch();
+  const size_t dig = merkle_words_per_tree(N, cap_height) * 8, cap = ((size_t)4 << cap_height) * 8;
+  CP_TRY(alloc_status(ctx, mem.alloc(&b.coeffs, k * n * 8), k * n * 8));
+  CP_TRY(alloc_status(ctx, mem.alloc(&b.lde, k * N * 8), k * N * 8));
+  CP_TRY(alloc_status(ctx, mem.alloc(&b.digests, dig), dig));
+  return alloc_status(ctx, mem.alloc(&b.cap, cap), cap);
 }
 int batch_alloc(cp_ctx *ctx, DevBatch &b, size_t Bn, size_t k, size_t n, size_t N, int cap_height) {
   b.k = k;
@@ -141,18 +135,14 @@ int fetch_flush(cp_ctx *ctx) {
 // page-locked staging area: at least `bytes` free, 64-byte aligned slots; the area is recycled at every flush
 int pin_reserve(cp_ctx *ctx, size_t bytes, char **out) {
   bytes = (bytes + 63) & ~(size_t)63;
-  if (ctx->pin_off + bytes > ctx->pin_bytes) {
+  if (ctx->pin_off + bytes > ctx->pin.bytes()) {
     CP_TRY(fetch_flush(ctx));  // everything staged so far has been consumed / delivered
-    if (bytes > ctx->pin_bytes) {
-      if (ctx->pin) (void)hipHostFree(ctx->pin);
-      ctx->pin = nullptr;
-      ctx->pin_bytes = 0;
-      size_t want = bytes < ((size_t)8 << 20) ? ((size_t)8 << 20) : bytes * 2;
-      if (hipHostMalloc((void **)&ctx->pin, want, hipHostMallocDefault) != hipSuccess) return set_error(ctx, CP_ERR_OOM, "hipHostMalloc failed");
-      ctx->pin_bytes = want;
+    if (bytes > ctx->pin.bytes()) {
+      const size_t want = bytes < ((size_t)8 << 20) ? ((size_t)8 << 20) : bytes * 2;
+      CP_TRY(alloc_status(ctx, ctx->pin.grow(want), want));
     }
   }
-  *out = ctx->pin + ctx->pin_off;
+  *out = ctx->pin.get<char>() + ctx->pin_off;
   ctx->pin_off += bytes;
   return CP_OK;
 }
@@ -226,6 +216,8 @@ struct cp_circuit {
   cp_ctx *ctx = nullptr;
   cp_shape sh;
   uint64_t digest[4];
+  explicit cp_circuit(cp_ctx *c) : ctx(c), mem(c->bag()) {}
+  DevBag mem;   // owns what cs, cs_values and k_is point to; waits for the context's stream before it frees
   DevBatch cs;  // constants + sigmas commitment (device resident for the circuit's lifetime)
   uint64_t *cs_values = nullptr;  // the same polynomials as VALUES over <omega_n> (sigma rows feed the Z computation)
   uint64_t *k_is = nullptr;       // num_routed_wires coset shifts
@@ -309,42 +301,31 @@ cp_circuit *cp_circuit_load(cp_ctx *ctx, const cp_shape *sh, const uint64_t circ
     set_error(ctx, CP_ERR_INVALID_ARG, "%s", why);
     return nullptr;
   }
-  cp_circuit *c = new (std::nothrow) cp_circuit();
+  std::unique_ptr<cp_circuit> c(new (std::nothrow) cp_circuit(ctx));
   if (!c) { set_error(ctx, CP_ERR_OOM, "out of host memory"); return nullptr; }
-  c->ctx = ctx;
   c->sh = *sh;
   memcpy(c->digest, circuit_digest, 32);
-  size_t n = (size_t)1 << sh->degree_bits, N = n << sh->rate_bits;
-  size_t k = (size_t)sh->num_constants + sh->num_routed_wires;
-  uint64_t *vals = nullptr;
-  int rc = batch_alloc_persistent(ctx, c->cs, k, n, N, sh->cap_height);
-  if (rc == CP_OK && dev_malloc(ctx->device, (void **)&vals, k * n * 8) != hipSuccess) rc = set_error(ctx, CP_ERR_OOM, "hipMalloc failed");
-  if (rc == CP_OK) rc = cp_h2d(ctx, vals, cs_values_host, k * n * 8);
-  if (rc == CP_OK)
-    rc = cp_commit_dev(ctx, vals, k, sh->degree_bits, sh->rate_bits, sh->cap_height, c->cs.coeffs, c->cs.lde,
-                       c->cs.digests, c->cs.cap);
-  if (rc == CP_OK) rc = batch_fetch_caps(ctx, c->cs, 1, sh->cap_height);
-  // coset shifts k_i of the routed wires (CommonCircuitData::k_is); plonky2's own choice is 7^i
-  if (rc == CP_OK && sh->num_routed_wires > 0) {
+  const int rc = [&]() -> int {
+    size_t n = (size_t)1 << sh->degree_bits, N = n << sh->rate_bits;
+    size_t k = (size_t)sh->num_constants + sh->num_routed_wires;
+    CP_TRY(batch_alloc_persistent(ctx, c->mem, c->cs, k, n, N, sh->cap_height));
+    CP_TRY(alloc_status(ctx, c->mem.alloc(&c->cs_values, k * n * 8), k * n * 8));
+    CP_TRY(cp_h2d(ctx, c->cs_values, cs_values_host, k * n * 8));
+    CP_TRY(cp_commit_dev(ctx, c->cs_values, k, sh->degree_bits, sh->rate_bits, sh->cap_height, c->cs.coeffs, c->cs.lde, c->cs.digests, c->cs.cap));
+    CP_TRY(batch_fetch_caps(ctx, c->cs, 1, sh->cap_height));
+    if (sh->num_routed_wires <= 0) return CP_OK;
+    // coset shifts k_i of the routed wires (CommonCircuitData::k_is); plonky2's own choice is 7^i
     std::vector<uint64_t> ks(sh->num_routed_wires);
     uint64_t acc = 1;
     for (int i = 0; i < sh->num_routed_wires; i++) {
       ks[i] = k_is_host ? k_is_host[i] : acc;
-      if (ks[i] >= gl::P) rc = set_error(ctx, CP_ERR_INVALID_ARG, "k_is[%d] is not canonical", i);
+      if (ks[i] >= gl::P) return set_error(ctx, CP_ERR_INVALID_ARG, "k_is[%d] is not canonical", i);
       acc = gl::mul(acc, 7);
     }
-    if (rc == CP_OK && dev_malloc(ctx->device, (void **)&c->k_is, ks.size() * 8) != hipSuccess) rc = set_error(ctx, CP_ERR_OOM, "hipMalloc failed");
-    if (rc == CP_OK) rc = cp_h2d(ctx, c->k_is, ks.data(), ks.size() * 8);
-  }
-  if (rc != CP_OK) {
-    if (vals) (void)hipFree(vals);
-    if (c->k_is) (void)hipFree(c->k_is);
-    batch_free_persistent(c->cs);
-    delete c;
-    return nullptr;
-  }
-  c->cs_values = vals;
-  return c;
+    CP_TRY(alloc_status(ctx, c->mem.alloc(&c->k_is, ks.size() * 8), ks.size() * 8));
+    return cp_h2d(ctx, c->k_is, ks.data(), ks.size() * 8);
+  }();
+  return rc == CP_OK ? c.release() : nullptr;
 } catch (...) {
   exception_status(ctx);
   return nullptr;
@@ -353,11 +334,7 @@ cp_circuit *cp_circuit_load(cp_ctx *ctx, const cp_shape *sh, const uint64_t circ
 void cp_circuit_destroy(cp_circuit *c) {
   if (!c) return;
   (void)hipSetDevice(c->ctx->device);
-  (void)hipStreamSynchronize(c->ctx->stream);
-  batch_free_persistent(c->cs);
-  if (c->cs_values) (void)hipFree(c->cs_values);
-  if (c->k_is) (void)hipFree(c->k_is);
-  delete c;
+  delete c;  // c->mem waits for the context's stream, then frees
 }
 
 // A7: Z / partial products for n_proofs proofs (same shape); betas, gammas: [proof][num_challenges] (host)
@@ -829,18 +806,11 @@ static int stage_host_inputs(cp_ctx *ctx, size_t n_proofs, cp_circuit *const *ci
   const size_t per = ((size_t)sh.num_wires << sh.degree_bits) * 8;
   const size_t per_salt = salts_host ? ((size_t)3 * CP_SALT_SIZE << (sh.degree_bits + sh.rate_bits)) * 8 : 0;
   const size_t need = (per + per_salt) * n_proofs;
-  if (ctx->wires_stage_bytes < need) {  // grows to the largest batch seen, then stays
-    (void)sync_stream(ctx);
-    if (ctx->wires_stage) (void)hipFree(ctx->wires_stage);
-    ctx->wires_stage = nullptr;
-    ctx->wires_stage_bytes = 0;
-    if (dev_malloc(ctx->device, (void **)&ctx->wires_stage, need) != hipSuccess) return set_error(ctx, CP_ERR_OOM, "hipMalloc of the wire staging buffer failed");
-    ctx->wires_stage_bytes = need;
-  }
-  char *salt_base = (char *)ctx->wires_stage + per * n_proofs;
+  CP_TRY(alloc_status(ctx, ctx->wires_stage.grow(need), need));  // grows to the largest batch seen, then stays
+  char *salt_base = ctx->wires_stage.get<char>() + per * n_proofs;
   for (size_t p = 0; p < n_proofs; p++) {
     if (!wires_values_host[p]) return set_error(ctx, CP_ERR_INVALID_ARG, "wires %zu are NULL", p);
-    if (hipMemcpyAsync((char *)ctx->wires_stage + p * per, wires_values_host[p], per, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    if (hipMemcpyAsync(ctx->wires_stage.get<char>() + p * per, wires_values_host[p], per, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
       return set_error(ctx, CP_ERR_HIP, "host-to-device copy of wires %zu failed", p);
     if (salts_host) {
       if (!salts_host[p]) return set_error(ctx, CP_ERR_INVALID_ARG, "salts %zu are NULL", p);
@@ -848,7 +818,7 @@ static int stage_host_inputs(cp_ctx *ctx, size_t n_proofs, cp_circuit *const *ci
         return set_error(ctx, CP_ERR_HIP, "host-to-device copy of salts %zu failed", p);
     }
   }
-  *wires_dev = ctx->wires_stage;
+  *wires_dev = ctx->wires_stage.get<uint64_t>();
   *salts_dev = salts_host ? (const uint64_t *)salt_base : nullptr;
   return CP_OK;
 }

@@ -1,52 +1,31 @@
 // Host side of the device-resident R1CS (kernels: r1cs.h): create validates, classifies and uploads a constraint system;
 // eval / check / prove-from-a-witness run on it. Included by bls.hip after groth16.inc.
 struct cp_r1cs_bls12381 {
-  int device = -1;
+  explicit cp_r1cs_bls12381(int dev) : device(dev), mem(dev_pool(), dev) {}
+  const int device;
   cp_r1cs_info info{};
   r1cs::System sys{};  // device pointers
   uint32_t *long_rows = nullptr;
   uint32_t n_long = 0;
-  std::vector<void *> owned;  // every device array of the handle
+  DevBag mem;  // every device array of the handle
 };
 
 namespace {
 
-// a buffer from the library's pool for the length of a call, handed back on every exit path. The stream is synchronised
-// first: only a buffer that no stream can still be using may enter the pool (dev_pool.h).
-struct PoolBufs {
-  cp_ctx *ctx;
-  std::vector<std::pair<void *, size_t>> bufs;
-  explicit PoolBufs(cp_ctx *c) : ctx(c) {}
-  ~PoolBufs() {
-    const bool idle = bufs.empty() || hipStreamSynchronize(ctx->stream) == hipSuccess;
-    for (auto &b : bufs) batch_pool_free(ctx->device, b.first, b.second, idle);
-  }
-  int alloc(size_t bytes, void **out) {
-    *out = nullptr;
-    bufs.reserve(bufs.size() + 1);
-    if (batch_pool_alloc(ctx->device, out, bytes) != hipSuccess) { *out = nullptr; return set_error(ctx, CP_ERR_OOM, "device allocation of %zu bytes failed", bytes); }
-    bufs.emplace_back(*out, bytes);
-    return CP_OK;
-  }
-};
-
 template <class T>
 int r1cs_upload(cp_ctx *ctx, cp_r1cs_bls12381 *h, const std::vector<T> &v, const T **out) {
-  void *d = nullptr;
+  T *d = nullptr;
   const size_t bytes = v.size() * sizeof(T);
-  h->owned.reserve(h->owned.size() + 1);
-  HIP_TRY(ctx, dev_malloc(ctx->device, &d, bytes ? bytes : 1));
-  h->owned.push_back(d);
+  CP_TRY(alloc_status(ctx, h->mem.alloc(&d, bytes ? bytes : 1), bytes));
   if (bytes) HIP_TRY(ctx, hipMemcpy(d, v.data(), bytes, hipMemcpyHostToDevice));
   h->info.device_bytes += bytes;
-  *out = (const T *)d;
+  *out = d;
   return CP_OK;
 }
 
 void r1cs_free(cp_r1cs_bls12381 *h) {
   if (!h) return;
-  if (!h->owned.empty()) (void)hipSetDevice(h->device);
-  for (void *p : h->owned) (void)hipFree(p);
+  if (h->mem.size()) (void)hipSetDevice(h->device);
   delete h;
 }
 
@@ -151,10 +130,10 @@ int r1cs_eval_run(cp_ctx *ctx, const cp_r1cs_bls12381 *h, const uint64_t *witnes
 // counts the violated rows; evals = NULL: evaluates the rows itself. Synchronises.
 int r1cs_check_run(cp_ctx *ctx, const cp_r1cs_bls12381 *h, const uint64_t *witness_dev, uint64_t *const evals[3], size_t *n_violated,
                    size_t *first_violated) {
-  PoolBufs pool(ctx);
+  DevBag pool = ctx->bag(DevOwn::POOLED);  // back to the pool on every exit path, as reusable once the stream is idle
   unsigned long long *counters = nullptr;
   uint32_t *long_vals = nullptr;
-  CP_TRY(pool.alloc(256, (void **)&counters));
+  CP_TRY(alloc_status(ctx, pool.alloc(&counters, 256), 256));
   const unsigned long long init[2] = {0, ~0ull};
   HIP_TRY(ctx, hipMemcpyAsync(counters, init, sizeof init, hipMemcpyHostToDevice, ctx->stream));
   const dim3 grid(blocks_for(h->sys.n, r1cs::THREADS)), block(r1cs::THREADS);
@@ -163,7 +142,7 @@ int r1cs_check_run(cp_ctx *ctx, const cp_r1cs_bls12381 *h, const uint64_t *witne
            (const uint32_t *)nullptr, (const uint32_t *)evals[0], (const uint32_t *)evals[1], (const uint32_t *)evals[2], counters);
   } else {
     if (h->n_long) {
-      CP_TRY(pool.alloc((size_t)h->n_long * 32, (void **)&long_vals));
+      CP_TRY(alloc_status(ctx, pool.alloc(&long_vals, (size_t)h->n_long * 32), (size_t)h->n_long * 32));
       CP_TRY(r1cs_eval_run(ctx, h, witness_dev, r1cs::Outputs{{nullptr, nullptr, nullptr}}, long_vals));
     }
     LAUNCH(ctx, "r1cs_check", r1cs::k_check<true>, grid, block, h->sys, (const uint32_t *)witness_dev, (const uint32_t *)h->long_rows, h->n_long,
@@ -185,8 +164,7 @@ cp_r1cs_bls12381 *cp_r1cs_bls12381_create(cp_ctx *ctx, const cp_r1cs_desc *desc)
   if (!ctx) { set_error(nullptr, CP_ERR_INVALID_ARG, "ctx is NULL"); return nullptr; }
   if (!desc) { set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: desc is NULL"); return nullptr; }
   if (hipSetDevice(ctx->device) != hipSuccess) { set_error(ctx, CP_ERR_HIP, "hipSetDevice failed"); return nullptr; }
-  cp_r1cs_bls12381 *h = new cp_r1cs_bls12381();
-  h->device = ctx->device;
+  cp_r1cs_bls12381 *h = new cp_r1cs_bls12381(ctx->device);
   struct Guard { cp_r1cs_bls12381 *h; ~Guard() { r1cs_free(h); } } guard{h};
   if (r1cs_build(ctx, desc, h) != CP_OK) return nullptr;
   guard.h = nullptr;
@@ -235,10 +213,10 @@ int cp_groth16_prove_r1cs_bls12381(cp_ctx *ctx, const cp_groth16_pk *pk, const c
     return set_error(ctx, CP_ERR_INVALID_ARG, "the proving key has n_wires = %zu, the R1CS %zu", pk->n_wires, r1cs->info.n_wires);
   if (pk->log_domain != r1cs->info.log_domain)
     return set_error(ctx, CP_ERR_INVALID_ARG, "the proving key has log_domain = %d, the R1CS %d", pk->log_domain, r1cs->info.log_domain);
-  PoolBufs pool(ctx);
+  DevBag pool = ctx->bag(DevOwn::POOLED);
   uint64_t *ev[3];
   const size_t bytes = r1cs->sys.n_pad * 32;
-  for (int k = 0; k < 3; k++) CP_TRY(pool.alloc(bytes, (void **)&ev[k]));
+  for (int k = 0; k < 3; k++) CP_TRY(alloc_status(ctx, pool.alloc(&ev[k], bytes), bytes));
   CP_TRY(r1cs_eval_run(ctx, r1cs, witness_dev, r1cs::Outputs{{(uint32_t *)ev[0], (uint32_t *)ev[1], (uint32_t *)ev[2]}}, nullptr));
   size_t n_violated = 0, first = 0;
   CP_TRY(r1cs_check_run(ctx, r1cs, witness_dev, ev, &n_violated, &first));

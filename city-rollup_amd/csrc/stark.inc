@@ -11,8 +11,7 @@ struct cp_air_program {
   air::Compiled single;  // the one-segment form (cp_air_program_get_info; map programs run it)
   struct Variant {
     air::Compiled C;
-    uint64_t *d_code = nullptr;
-    uint32_t *d_seg_off = nullptr;
+    DevBuf d_code, d_seg_off;  // uint64_t / uint32_t
   };
   std::mutex m;
   std::map<uint32_t, Variant> variants;  // segments asked for -> the compiled form on the device
@@ -48,19 +47,13 @@ int air_variant(cp_ctx *ctx, cp_air_program *prog, uint32_t want, const cp_air_p
     }
     if (v.C.n_slots >= air::DST_NONE) return set_error(ctx, CP_ERR_UNSUPPORTED, "the program needs %u live temporaries (limit %u)", v.C.n_slots, air::DST_NONE - 1);
     const size_t cb = (v.C.code.size() ? v.C.code.size() : 1) * 8, sb = v.C.seg_off.size() * 4;
-    HIP_TRY(ctx, dev_malloc(prog->device, (void **)&v.d_code, cb));
-    if (dev_malloc(prog->device, (void **)&v.d_seg_off, sb) != hipSuccess) {
-      (void)hipFree(v.d_code);
-      return set_error(ctx, CP_ERR_OOM, "out of device memory for a compiled AIR program");
-    }
-    hipError_t e = hipMemcpyAsync(v.d_code, v.C.code.data(), v.C.code.size() * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v.d_seg_off, v.C.seg_off.data(), sb, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the host vectors may move when the map grows
-    if (e != hipSuccess) {
-      (void)hipFree(v.d_code);
-      (void)hipFree(v.d_seg_off);
-      return set_error(ctx, CP_ERR_HIP, "upload of a compiled AIR program failed: %s", hipGetErrorString(e));
-    }
+    v.d_code = DevBuf(dev_pool(), prog->device);
+    v.d_seg_off = DevBuf(dev_pool(), prog->device);
+    CP_TRY(alloc_status(ctx, v.d_code.alloc(cb), cb));
+    CP_TRY(alloc_status(ctx, v.d_seg_off.alloc(sb), sb));
+    HIP_TRY(ctx, hipMemcpyAsync(v.d_code.get(), v.C.code.data(), v.C.code.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(v.d_seg_off.get(), v.C.seg_off.data(), sb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the host vectors may move when the map grows
     it = prog->variants.emplace(want, std::move(v)).first;
   }
   *out = &it->second;
@@ -71,7 +64,7 @@ int air_variant(cp_ctx *ctx, cp_air_program *prog, uint32_t want, const cp_air_p
 int air_selectors(cp_ctx *ctx, int db, int q, const uint64_t **out) {
   auto key = std::make_pair(db, q);
   auto it = ctx->air_sel_tables.find(key);
-  if (it != ctx->air_sel_tables.end()) { *out = it->second; return CP_OK; }
+  if (it != ctx->air_sel_tables.end()) { *out = it->second.get<uint64_t>(); return CP_OK; }
   const int log_M = db + q;
   const size_t M = (size_t)1 << log_M, n = (size_t)1 << db;
   uint64_t wM = gl::pow(7, (gl::P - 1) >> 32);
@@ -80,13 +73,12 @@ int air_selectors(cp_ctx *ctx, int db, int q, const uint64_t **out) {
   for (int i = 0; i < q; i++) g = gl::sqr(g);
   const uint64_t *otab = nullptr;
   CP_TRY(get_pow_table(ctx, wM, &otab));
-  uint64_t *tab = nullptr;
-  HIP_TRY(ctx, dev_malloc(ctx->device, (void **)&tab, 3 * M * 8));
-  hipLaunchKernelGGL(air::k_selectors, dim3(blocks_for(M, 256)), dim3(256), 0, ctx->stream, tab, M, log_M, db, otab, gl::pow(g, n - 1),
-                     gl::inv((uint64_t)n % gl::P));
-  if (hipGetLastError() != hipSuccess) { (void)hipFree(tab); return set_error(ctx, CP_ERR_HIP, "selector table launch failed"); }
-  ctx->air_sel_tables[key] = tab;
-  *out = tab;
+  DevBuf tab = ctx->buf();
+  CP_TRY(alloc_status(ctx, tab.alloc(3 * M * 8), 3 * M * 8));
+  LAUNCH(ctx, "air_selectors", air::k_selectors, dim3(blocks_for(M, 256)), dim3(256), tab.get<uint64_t>(), M, log_M, db, otab, gl::pow(g, n - 1),
+         gl::inv((uint64_t)n % gl::P));
+  *out = tab.get<uint64_t>();
+  ctx->air_sel_tables[key] = std::move(tab);
   return CP_OK;
 }
 
@@ -147,8 +139,8 @@ int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::
   const uint32_t lds_fit = (uint32_t)std::min<size_t>(lds_max / ((size_t)K * air::WAVE * 8), air::DST_NONE);
   if (lds_fit < 1) return set_error(ctx, CP_ERR_UNSUPPORTED, "one AIR slot (%zu B) exceeds the device's %zu B of LDS per workgroup", (size_t)K * air::WAVE * 8, lds_max);
   const uint32_t n_lds = std::min({V.C.n_slots, air_lds_slots(ctx), lds_fit}), n_spill = V.C.n_slots - n_lds;
-  ka.code = V.d_code;
-  ka.seg_off = V.d_seg_off;
+  ka.code = V.d_code.get<uint64_t>();
+  ka.seg_off = V.d_seg_off.get<uint32_t>();
   ka.n_lds = (int)n_lds;
   ka.spill_stride = (size_t)S * blocks * K * air::WAVE;
   ka.spill = nullptr;
@@ -291,10 +283,6 @@ cp_air_program *cp_air_program_create(cp_ctx *ctx, const cp_air_program_desc *de
 void cp_air_program_destroy(cp_air_program *p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  for (auto &kv : p->variants) {
-    (void)hipFree(kv.second.d_code);
-    (void)hipFree(kv.second.d_seg_off);
-  }
   delete p;
 }
 
@@ -491,22 +479,20 @@ int cp_stark_prove(cp_ctx *ctx, const cp_stark_desc *desc, const uint64_t *trace
   const size_t cap_w = (size_t)4 << s.ch;
   // every handle and buffer of the call, released on every exit path
   struct Owned {
-    int device;
+    DevBuf vals_buf;  // from the pool; goes back as reusable only once the stream is known to be idle (after the handles below)
     cp_poly_batch *t0 = nullptr, *t1 = nullptr, *qb = nullptr;
     uint64_t *vals = nullptr;
-    size_t vals_bytes = 0;
     uint8_t *fri = nullptr;
     ~Owned() {
       cp_batch_destroy(t0);
       cp_batch_destroy(t1);
       cp_batch_destroy(qb);
-      batch_pool_free(device, vals, vals_bytes, true);
       free(fri);
     }
-  } own{ctx->device};
+  } own{ctx->buf(DevOwn::POOLED)};
   // the value columns of both trace rounds in one array: a row of a map step = execution trace, then the extended columns
-  own.vals_bytes = s.kt * s.n * 8;
-  HIP_TRY(ctx, batch_pool_alloc(ctx->device, (void **)&own.vals, own.vals_bytes));
+  CP_TRY(alloc_status(ctx, own.vals_buf.alloc(s.kt * s.n * 8), s.kt * s.n * 8));
+  own.vals = own.vals_buf.get<uint64_t>();
   if (trace_on_device) CP_TRY(cp_d2d(ctx, own.vals, trace_values, s.k0 * s.n * 8));
   else {
     CP_TRY(cp_h2d(ctx, own.vals, trace_values, s.k0 * s.n * 8));
@@ -574,6 +560,7 @@ int cp_stark_prove(cp_ctx *ctx, const cp_stark_desc *desc, const uint64_t *trace
   *proof_out = buf;
   *proof_len = b.size();
   *challenger = ch;
+  own.vals_buf.mark_idle();  // cp_fri_prove drained the stream and nothing was enqueued since
   return CP_OK;
 } CP_CATCH(ctx)
 

@@ -387,6 +387,58 @@ int hs_pool_script(size_t n_devices, size_t pool_cap, size_t capacity, const int
 }
 }
 
+// ---- dev_mem.h: the owners over the same counting allocator. ops: n x {op, a, b, c}:
+//  0 new(slot a, pooled b, with the idle callback c)   1 alloc(slot a, bytes b) -> 0 / -OOM   2 grow(slot a, bytes b) -> 0 / -OOM
+//  3 reset(slot a)   4 move(slot a -> slot b)   5 the idle callback answers a from now on   6 mark_idle(slot a)   7 mark_exported(slot a)
+//  8 release(slot a): the caller takes the pointer (and frees it through the runtime)   9 bag(pooled a, b allocations of c bytes, callback
+//  always) -> how many succeeded before the first refusal; the bag dies with the op   10 size(slot a) -> bytes, -1 if pointer and size disagree
+// Every owner dies before the counters are read: the pool script's ten, then how often the idle callback was asked.
+#include "../../city-rollup_amd/csrc/dev_mem.h"
+extern "C" {
+int hs_mem_script(size_t pool_cap, size_t capacity, const int64_t *ops, size_t n, int64_t *results, uint64_t *counters_out) {
+  using poolsim::Fake;
+  using Pool = DevPoolT<Fake>;
+  Fake::capacity = capacity; Fake::in_use = 0; Fake::n_malloc = Fake::n_free = Fake::n_oom = 0; Fake::live.clear();
+  Pool pool(1, pool_cap);
+  bool answer = true;
+  uint64_t asked = 0;
+  const auto idle = [&] { asked++; return answer; };
+  {
+    std::vector<DevBufT<Pool>> slots(8);
+    for (size_t i = 0; i < n; i++) {
+      const int64_t op = ops[4 * i], a = ops[4 * i + 1], b = ops[4 * i + 2], c = ops[4 * i + 3];
+      results[i] = 0;
+      if (op != 5 && op != 9 && (a < 0 || a >= 8)) return -1;
+      if (op == 0) slots[a] = c ? DevBufT<Pool>(pool, 0, b ? DevOwn::POOLED : DevOwn::RUNTIME, idle) : DevBufT<Pool>(pool, 0, b ? DevOwn::POOLED : DevOwn::RUNTIME);
+      else if (op == 1) results[i] = -slots[a].alloc((size_t)b);
+      else if (op == 2) results[i] = -slots[a].grow((size_t)b);
+      else if (op == 3) slots[a].reset();
+      else if (op == 4) { if (b < 0 || b >= 8) return -1; slots[b] = std::move(slots[a]); }
+      else if (op == 5) answer = a != 0;
+      else if (op == 6) slots[a].mark_idle();
+      else if (op == 7) slots[a].mark_exported();
+      else if (op == 8) { void *p = slots[a].release(); if (p) Pool::free(p); }
+      else if (op == 9) {
+        DevBagT<Pool> bag(pool, 0, a ? DevOwn::POOLED : DevOwn::RUNTIME, idle);
+        for (int64_t k = 0; k < b; k++) {
+          char *q;
+          if (bag.alloc(&q, (size_t)c)) { if (q) return -2; break; }
+          results[i]++;
+        }
+        if ((int64_t)bag.size() != results[i]) return -2;
+      } else if (op == 10) results[i] = ((bool)slots[a] == (slots[a].bytes() != 0)) ? (int64_t)slots[a].bytes() : -1;
+    }
+  }
+  counters_out[0] = Fake::in_use; counters_out[1] = Fake::n_malloc; counters_out[2] = Fake::n_free; counters_out[3] = Fake::n_oom;
+  counters_out[4] = Fake::live.size();
+  counters_out[5] = pool.stats(0).bytes; counters_out[6] = pool.stats(1).bytes;
+  counters_out[7] = pool.stats(0).hits; counters_out[8] = pool.stats(0).misses; counters_out[9] = pool.stats(0).trims;
+  counters_out[10] = asked;
+  pool.trim(0);  // what the pool still parks goes back too: after this nothing may be live
+  return Fake::live.empty() && Fake::n_free != (size_t)-1 ? 0 : -3;
+}
+}
+
 // ---- air.h: the host half (analyse + compile) and the instruction semantics the device interpreter shares (run_segment),
 // executed on one row / point with plain arrays behind the memory interface ----
 #include <cstdio>

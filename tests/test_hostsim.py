@@ -513,3 +513,91 @@ def test_batch_buffer_pool_logic(hs):
                                                                                  for o in ops if o[0] == REL)
         assert c["in_use"] == held + c["pooled0"] + c["pooled1"]
         assert c["n_free"] != 2**64 - 1
+
+
+def _mem_script(hs, pool_cap, capacity, ops):
+    hs.hs_mem_script.argtypes = [ctypes.c_size_t] * 2 + [ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64),
+                                                         ctypes.POINTER(ctypes.c_uint64)]
+    a = np.array(ops, dtype=np.int64).reshape(-1, 4)
+    res = np.zeros(len(a), np.int64)
+    cnt = np.zeros(11, np.uint64)
+    rc = hs.hs_mem_script(pool_cap, capacity, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(a),
+                          res.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    assert rc == 0, {-1: "bad script", -2: "the bag and its results disagree", -3: "a leak or a double free"}[rc]
+    keys = ("in_use", "n_malloc", "n_free", "n_oom", "live", "pooled0", "pooled1", "hits0", "misses0", "trims0", "asked")
+    c = dict(zip(keys, (int(v) for v in cnt)))
+    # after every script: every owner is dead, so what the runtime still holds is exactly what the pool parks, and no
+    # pointer was freed twice (the driver itself then trims the pool and requires an empty allocator: rc == 0 above)
+    assert c["n_free"] != 2**64 - 1 and c["in_use"] == c["pooled0"] and c["n_malloc"] - c["n_free"] == c["live"]
+    return [int(v) for v in res], c
+
+
+def test_device_memory_owners(hs):
+    """city-rollup_amd/csrc/dev_mem.h over the counting allocator of the pool test: the two ways of giving a buffer back, moves, the
+    grow-only pattern and its failure, the idle rule (a buffer whose callback said no, or that was exported, never reaches
+    the pool), release, and the scope bag with a refusal in the middle. No script may leak or free twice."""
+    NEW, ALLOC, GROW, RESET, MOVE, ANSWER, IDLE, EXPORT, RELEASE, BAG, SIZE = range(11)
+    MB = 1 << 20
+    BIG = 1 << 40
+    # runtime-owned: malloc and free, the pool never sees it and nobody is asked; moving moves the one buffer
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 0, 1), (ALLOC, 0, MB, 0), (MOVE, 0, 1, 0), (SIZE, 0, 0, 0), (SIZE, 1, 0, 0), (RESET, 1, 0, 0)])
+    assert res[1] == 0 and res[3] == 0 and res[4] == MB
+    assert c["n_malloc"] == 1 and c["n_free"] == 1 and c["pooled0"] == 0 and c["misses0"] == 0 and c["asked"] == 0
+    # pool-owned, the callback says yes: parked, and handed out again to the next owner
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 1, 1), (ALLOC, 0, MB, 0), (RESET, 0, 0, 0), (NEW, 1, 1, 1), (ALLOC, 1, MB, 0)])
+    assert c["n_malloc"] == 1 and c["n_free"] == 0 and c["hits0"] == 1 and c["asked"] == 2 and c["pooled0"] == MB
+    # the callback says no / no callback at all / exported (whatever is said afterwards): never into the pool, one runtime free
+    for tail in ([(ANSWER, 0, 0, 0)], [], [(EXPORT, 0, 0, 0), (IDLE, 0, 0, 0)]):
+        with_cb = 0 if tail == [] else 1
+        res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 1, with_cb), (ALLOC, 0, MB, 0)] + tail + [(RESET, 0, 0, 0)])
+        assert c["pooled0"] == 0 and c["n_free"] == 1 and c["n_malloc"] == 1, tail
+    assert c["asked"] == 0   # an exported buffer asks nobody
+    # marked idle: into the pool without asking, also when the callback would have said no
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 1, 1), (ALLOC, 0, MB, 0), (ANSWER, 0, 0, 0), (IDLE, 0, 0, 0), (RESET, 0, 0, 0)])
+    assert c["pooled0"] == MB and c["n_free"] == 0 and c["asked"] == 0
+    # moved pool-owned buffer keeps its way back and its mark; the moved-from owner is empty; destruction gives it back
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 1, 1), (ALLOC, 0, MB, 0), (EXPORT, 0, 0, 0), (MOVE, 0, 3, 0), (SIZE, 0, 0, 0), (SIZE, 3, 0, 0)])
+    assert res[4] == 0 and res[5] == MB and c["pooled0"] == 0 and c["n_free"] == 1
+    # move onto a full owner gives the target's buffer back first
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 0, 0), (ALLOC, 0, MB, 0), (NEW, 1, 0, 0), (ALLOC, 1, 2 * MB, 0), (MOVE, 0, 1, 0), (SIZE, 1, 0, 0)])
+    assert res[5] == MB and c["n_free"] == 2
+    # grow: larger waits (one question) and reallocates, smaller or equal does nothing
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 0, 1), (GROW, 0, MB, 0), (GROW, 0, 2 * MB, 0), (GROW, 0, MB, 0), (GROW, 0, 2 * MB, 0), (SIZE, 0, 0, 0)])
+    assert res[1:5] == [0, 0, 0, 0] and res[5] == 2 * MB and c["n_malloc"] == 2 and c["n_free"] == 2 and c["asked"] == 1
+    # grow with the allocator out of capacity: the old buffer is gone, the owner empty with size 0, and it can grow again
+    res, c = _mem_script(hs, 64 * MB, 3 * MB, [(NEW, 0, 0, 1), (GROW, 0, 2 * MB, 0), (GROW, 0, 4 * MB, 0), (SIZE, 0, 0, 0), (GROW, 0, 3 * MB, 0), (SIZE, 0, 0, 0)])
+    assert res[1] == 0 and res[2] == -2 and res[3] == 0 and res[4] == 0 and res[5] == 3 * MB and c["n_oom"] == 1
+    # a pool-owned grow obeys the idle rule for the old buffer: callback no -> runtime free
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 1, 1), (GROW, 0, MB, 0), (ANSWER, 0, 0, 0), (GROW, 0, 2 * MB, 0), (ANSWER, 1, 0, 0), (RESET, 0, 0, 0)])
+    assert c["pooled0"] == 2 * MB and c["n_free"] == 1
+    # release: the owner forgets the buffer (the caller frees it), nothing is freed twice
+    res, c = _mem_script(hs, 64 * MB, BIG, [(NEW, 0, 0, 0), (ALLOC, 0, MB, 0), (RELEASE, 0, 0, 0), (SIZE, 0, 0, 0), (RESET, 0, 0, 0)])
+    assert res[3] == 0 and c["n_malloc"] == 1 and c["n_free"] == 1
+    # the bag: one question for all its buffers; a refusal in the middle (capacity for two of four) strands nothing
+    res, c = _mem_script(hs, 64 * MB, BIG, [(BAG, 1, 3, MB)])
+    assert res[0] == 3 and c["asked"] == 1 and c["pooled0"] == 3 * MB and c["n_free"] == 0
+    res, c = _mem_script(hs, 64 * MB, BIG, [(ANSWER, 0, 0, 0), (BAG, 1, 3, MB)])
+    assert res[1] == 3 and c["asked"] == 1 and c["pooled0"] == 0 and c["n_free"] == 3
+    for pooled in (0, 1):
+        res, c = _mem_script(hs, 64 * MB, 2 * MB + 1, [(BAG, pooled, 4, MB)])
+        assert res[0] == 2 and c["n_oom"] == 1 and c["n_malloc"] == 2 and c["n_free"] == (0 if pooled else 2) and c["pooled0"] == (2 * MB if pooled else 0)
+    res, c = _mem_script(hs, 64 * MB, BIG, [(BAG, 0, 0, MB)])
+    assert c["asked"] == 0   # an empty bag waits for nothing
+    # random scripts: the books balance whatever the order (_mem_script asserts it), with a capacity that refuses now and then
+    rng = np.random.default_rng(7)
+    for _ in range(50):
+        ops = [(NEW, s_, int(rng.integers(0, 2)), int(rng.integers(0, 2))) for s_ in range(8)]
+        for _ in range(200):
+            op = int(rng.choice([ALLOC, GROW, RESET, MOVE, ANSWER, IDLE, EXPORT, RELEASE, BAG, SIZE, NEW]))
+            a, b, c_ = int(rng.integers(0, 8)), int(rng.integers(0, 8)), 0
+            if op in (ALLOC, GROW):
+                b = int(rng.choice([1, 2, 4, 8])) * MB
+            elif op == BAG:
+                a, b, c_ = int(rng.integers(0, 2)), int(rng.integers(0, 5)), int(rng.choice([1, 2, 4])) * MB
+            elif op == NEW:
+                b, c_ = int(rng.integers(0, 2)), int(rng.integers(0, 2))
+            elif op == ANSWER:
+                a = int(rng.integers(0, 2))
+            ops.append((op, a, b, c_))
+        res, c = _mem_script(hs, 16 * MB, 24 * MB, ops)
+        assert all(r >= 0 or r == -2 for r in res)   # -2: the allocator's out-of-memory, never a disagreement of pointer and size
