@@ -63,12 +63,28 @@ GL_HD uint64_t add_lazy(uint64_t a, uint64_t b) {
   return s;
 }
 
-// A modular multiplication is 12 VALU instructions on gfx950: 4 v_mad_u64_u32 for the product (+ 2 moves, 1 select), 2 for
-// `lo - w3`, one more multiply-add for `+ w2 (2^32 - 1)` (+ select, 64-bit add). Three pieces are written as `asm` because
-// carry-outs are out of the compiler's reach (it zero-extends, adds and compares instead: 19 instructions; the permutation
-// measures 2.06 -> 2.48 -> 2.62 G/s with them, tools/ubench_poseidon_variants.hip). The `s_nop 1` are the two wait states
-// gfx950 needs between a VALU write of an SGPR and a VALU read of it; the compiler's hazard recogniser does not look inside
-// `asm`. tests/test_gpu_parity.py drives `cp_field_mul` through every carry / borrow corner on the device.
+// A modular multiplication is 11 VALU instructions on gfx950: 4 v_mad_u64_u32 for the product (+ 2 moves), 2 for the borrow
+// chain `lo - w3`, one more multiply-add for `+ w2 (2^32 - 1)` (+ select, 64-bit add). Three pieces are written as `asm`
+// because carry-outs are out of the compiler's reach (it zero-extends, adds and compares instead: 19 instructions; the
+// permutation measures 2.06 -> 2.48 -> 2.62 G/s with them, tools/ubench_poseidon_variants.hip).
+//
+// The carry-out `cy` of the third multiply-add (`mul_wide_cy`) has weight 2^96 == -1: it is a unit to subtract, and it never
+// becomes a VGPR. It stays in the SGPR pair the multiply-add wrote and enters the borrow chain of the reduction as the
+// carry-in of its first subtract (`reduce128_lazy(lo, hi', cy)`), where hi' is the high half WITHOUT that carry. What makes
+// this sound, with a = a1 2^32 + a0, b likewise, r = a1 b0 + p01 mod 2^64 and hi' = a1 b1 + hi32(r):
+//   1. hi' cannot carry: a1 b1 + hi32(r) <= (2^32 - 1)^2 + 2^32 - 1 = 2^64 - 2^32. The true high half is hi = hi' + cy 2^32.
+//   2. hi32(hi') + cy <= 2^32 - 1: adding cy 2^32 to hi' does not touch its low word, so hi32(hi') + cy = hi32(hi), and
+//      hi <= 2^64 - 2 because a b <= (2^64 - 1)^2. `mul_add_lazy` adds the carry of lo + c to hi' first: a b + c <=
+//      (2^64 - 1) 2^64 keeps hi + 1 <= 2^64 - 1, so hi' + 1 cannot carry either and hi32(hi' + 1) + cy = hi32(hi + 1) <=
+//      2^32 - 1. The chain therefore subtracts exactly the old w3 = hi32(hi), and borrows for exactly the same operands
+//      (lo < w3) as the two-argument form.
+//   3. the repaired t0 cannot underflow: a borrow means lo < w3 <= 2^32 - 1, so t0 = lo - w3 + 2^64 >= 2^64 - 2^32 + 1 > EPS.
+//   4. the fold cannot wrap twice: t0 + w2 (2^32 - 1) < 2^65 - 2^33, so after one wrap (+ EPS) it is below 2^64 - 2^33.
+//
+// The `s_nop 1` are the two wait states gfx950 needs between a VALU write of an SGPR and a VALU read of it; the compiler's
+// hazard recogniser does not look inside `asm`, so every statement that reads such an SGPR (`cy` comes from ANOTHER
+// statement) carries its own wait states in front of the read. tests/test_gpu_parity.py drives `cp_field_mul` through every
+// carry / borrow corner on the device, tests/test_gpu_product_chain.py every class of (cy, borrow, fold wrap).
 
 // lo + top * (2^32 - 1) as a lazy u64 (top * 2^64 == top * (2^32 - 1))
 GL_HD uint64_t fold_top(uint64_t lo, uint32_t top) {
@@ -110,7 +126,8 @@ GL_HD uint64_t reduce128_lazy(uint64_t lo, uint64_t hi) {
 }
 GL_HD uint64_t reduce128(uint64_t lo, uint64_t hi) { return canon(reduce128_lazy(lo, hi)); }
 
-// 64x64 -> 128 as exactly four 32x32+64 multiply-adds (v_mad_u64_u32)
+// 64x64 -> 128 as exactly four 32x32+64 multiply-adds (v_mad_u64_u32): the true 128-bit value, for callers that go on adding
+// to it (poseidon_coop.h's dot product); a modular product takes `mul_wide_cy` below
 GL_HD void mul_wide(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi) {
   const uint32_t a0 = lo32(a), a1 = hi32(a), b0 = lo32(b), b1 = hi32(b);
   const uint64_t p00 = (uint64_t)a0 * b0;
@@ -133,19 +150,71 @@ GL_HD void mul_wide(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi) {
 #endif
 }
 
+// The carry-aware pair (see the comment above `fold_top`). `carry_t` is the carry-out of the product's third multiply-add:
+// on the device the SGPR pair that instruction wrote (one bit per lane), only ever handed from `mul_wide_cy` to
+// `reduce128_lazy`; in the portable form `hi` is the true high half and the carry is 0.
+typedef uint64_t carry_t;
+
+// a * b = lo + (hi + cy 2^32) 2^64
+GL_HD void mul_wide_cy(uint64_t a, uint64_t b, uint64_t &lo, uint64_t &hi, carry_t &cy) {
+#if GL_DEVICE_ASM
+  const uint32_t a0 = lo32(a), a1 = hi32(a), b0 = lo32(b), b1 = hi32(b);
+  const uint64_t p00 = (uint64_t)a0 * b0;
+  const uint64_t p01 = (uint64_t)a0 * b1 + (p00 >> 32);  // < 2^64
+  uint64_t r;
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(r), "=&s"(cy) : "v"(a1), "v"(b0), "v"(p01));
+  lo = pack(lo32(p00), lo32(r));
+  hi = (uint64_t)a1 * b1 + (uint64_t)hi32(r);  // (1): no carry
+#else
+  mul_wide(a, b, lo, hi);
+  cy = 0;
+#endif
+}
+
+// (lo, hi', cy) -> lazy u64: lo - (hi32(hi') + cy) + lo32(hi') (2^32 - 1), every wrap of 2^64 repaid by -+EPS
+GL_HD uint64_t reduce128_lazy(uint64_t lo, uint64_t hi, carry_t cy) {
+#if GL_DEVICE_ASM
+  // `cy` is the carry-in of the low-word subtract (2); the rare borrow (lo < w3) keeps its wave-uniform branch (3)
+  uint32_t tl, th, m;
+  uint64_t bm;
+  asm("s_nop 1\n\tv_subb_co_u32_e64 %0, %2, %3, %4, %6\n\ts_nop 1\n\tv_subbrev_co_u32_e64 %1, %2, 0, %5, %2"
+      : "=&v"(tl), "=&v"(th), "=&s"(bm)
+      : "v"(lo32(lo)), "v"(hi32(hi)), "v"(hi32(lo)), "s"(cy));
+  uint64_t t0 = pack(tl, th);
+  if (__builtin_expect(bm != 0, 0)) {
+    asm volatile("v_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(bm));
+    t0 -= m;
+  }
+  return fold_top(t0, lo32(hi));
+#else
+  (void)cy;
+  return reduce128_lazy(lo, hi);
+#endif
+}
+GL_HD uint64_t reduce128(uint64_t lo, uint64_t hi, carry_t cy) { return canon(reduce128_lazy(lo, hi, cy)); }
+
+// a*b as a lazy u64; a, b may be lazy themselves
+GL_HD uint64_t mul_lazy(uint64_t a, uint64_t b) {
+  uint64_t lo, hi;
+  carry_t cy;
+  mul_wide_cy(a, b, lo, hi, cy);
+  return reduce128_lazy(lo, hi, cy);
+}
 GL_HD uint64_t mul(uint64_t a, uint64_t b) {
   uint64_t lo, hi;
-  mul_wide(a, b, lo, hi);
-  return reduce128(lo, hi);
+  carry_t cy;
+  mul_wide_cy(a, b, lo, hi, cy);
+  return reduce128(lo, hi, cy);
 }
 GL_HD uint64_t sqr(uint64_t a) { return mul(a, a); }
 // a*b + c as a lazy u64 (any representative < 2^64 of the class); a, b, c may be lazy themselves
 GL_HD uint64_t mul_add_lazy(uint64_t a, uint64_t b, uint64_t c) {
   uint64_t lo, hi;
-  mul_wide(a, b, lo, hi);
+  carry_t cy;
+  mul_wide_cy(a, b, lo, hi, cy);
   lo += c;
-  hi += lo < c;  // a*b <= (2^64-1)^2 keeps hi <= 2^64-2: no overflow
-  return reduce128_lazy(lo, hi);
+  hi += lo < c;  // (2): a*b + c <= (2^64-1) 2^64 keeps the true high half <= 2^64-1, and hi' below it
+  return reduce128_lazy(lo, hi, cy);
 }
 
 GL_HD uint64_t pow7(uint64_t x) {
@@ -172,10 +241,7 @@ GL_HD Ext ext_add(Ext x, Ext y) { return {add(x.a, y.a), add(x.b, y.b)}; }
 GL_HD Ext ext_sub(Ext x, Ext y) { return {sub(x.a, y.a), sub(x.b, y.b)}; }
 GL_HD Ext ext_mul(Ext x, Ext y) {
   uint64_t bb = mul(x.b, y.b);
-  // 7*bb
-  uint64_t lo, hi;
-  mul_wide(bb, 7, lo, hi);
-  return {add(mul(x.a, y.a), reduce128(lo, hi)), add(mul(x.a, y.b), mul(x.b, y.a))};
+  return {add(mul(x.a, y.a), mul(bb, 7)), add(mul(x.a, y.b), mul(x.b, y.a))};
 }
 GL_HD Ext ext_scale(Ext x, uint64_t s) { return {mul(x.a, s), mul(x.b, s)}; }
 

@@ -102,11 +102,7 @@ GL_HD void round16(uint64_t (&x)[16], uint64_t T3) {
     uint64_t pw = T3;  // T3^e, lazy from the second on (a product takes any u64)
 #pragma unroll
     for (int e = 1; e < (1 << NSTAGES); e++) {
-      if (e > 1) {
-        uint64_t lo, hi;
-        gl::mul_wide(pw, T3, lo, hi);
-        pw = gl::reduce128_lazy(lo, hi);
-      }
+      if (e > 1) pw = gl::mul_lazy(pw, T3);
 #pragma unroll
       for (int m = 0; m < 16; m++) {
         int em = 0;  // e(m): bit B of m (B = 3 .. 4 - NSTAGES) weighs 2^(3 - B)
@@ -257,11 +253,7 @@ __global__ __launch_bounds__(THREADS, (HALF && !(L == 4 && !ROWS)) ? NTT16_MIN_W
         for (int j = 0; j < 16; j++) {
           const int m = ((j & 1) << 3) | ((j & 2) << 1) | ((j & 4) >> 1) | ((j & 8) >> 3);
           x[m] = gl::mul(x[m], w);
-          if (j < 15) {  // the running power stays lazy: a product takes any u64
-            uint64_t wl, wh;
-            gl::mul_wide(w, G, wl, wh);
-            w = gl::reduce128_lazy(wl, wh);
-          }
+          if (j < 15) w = gl::mul_lazy(w, G);  // the running power stays lazy: a product takes any u64
         }
       }
     }

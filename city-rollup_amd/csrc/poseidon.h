@@ -6,7 +6,7 @@
 //
 // One lane owns one 12-element state (24 VGPRs): no cross-lane traffic, integer and fp64 VALU only, bound by instruction
 // issue. What shapes the code (measured on MI355X, profiles/r01_ubench_valu.txt, r02_ubench_poseidon.txt):
-//   * a 64-bit modular multiplication is 12 instructions (gl.h: `mul_wide`, `reduce128_lazy`, `fold_top` — three pieces in `asm`);
+//   * a 64-bit modular multiplication is 11 instructions (gl.h: `mul_wide_cy`, `reduce128_lazy`, `fold_top` — three pieces in `asm`);
 //   * the MDS layer (circulant, entries <= 41, + diag 8) uses NO integer multiplies at all: the length-12 cyclic
 //     convolution is evaluated per limb plane through the CRT split
 //         x^12-1 = (x^6-1)(x^6+1),  x^6-1 = (x^3-1)(x^3+1)
@@ -82,11 +82,7 @@ enum : int {
 };
 // ---- lazy field helpers: inputs/outputs are arbitrary u64 congruent to the value ----------
 using gl::fold_top;
-GL_HD uint64_t mul_lazy(uint64_t a, uint64_t b) {
-  uint64_t lo, hi;
-  gl::mul_wide(a, b, lo, hi);
-  return gl::reduce128_lazy(lo, hi);
-}
+using gl::mul_lazy;
 GL_HD uint64_t sbox_lazy(uint64_t x) {
   const uint64_t x2 = mul_lazy(x, x), x4 = mul_lazy(x2, x2), x3 = mul_lazy(x, x2);
   return mul_lazy(x3, x4);
