@@ -1342,8 +1342,11 @@ ABI.update({
     "cp_column_prefix_sum_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int]),
     "cp_stark_prove": (ctypes.c_int, [_vp, ctypes.POINTER(StarkDesc), _vp, ctypes.c_int, _u64p, _u64p, ctypes.POINTER(ChallengerState), ctypes.c_int,
                                       ctypes.c_uint64, _u8pp, ctypes.POINTER(ctypes.c_size_t)]),
+    "cp_stark_prove_batch": (ctypes.c_int, [_vp, ctypes.POINTER(StarkDesc), ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.c_int, _u64p, _u64p,
+                                            ctypes.POINTER(ChallengerState), ctypes.POINTER(ctypes.c_int), _u64p, _u8pp, ctypes.POINTER(ctypes.c_size_t)]),
     "cp_stark_verify": (ctypes.c_int, [ctypes.POINTER(StarkDesc), _u64p, _u64p, ctypes.POINTER(ChallengerState), ctypes.c_char_p, ctypes.c_size_t]),
 })
+STARK_BATCH_MAX = 64
 
 
 def _opt_u64(x):
@@ -1478,6 +1481,35 @@ def stark_prove(prover, desc, trace, challenger, publics=None, globals_=None, po
         return ctypes.string_at(out, ln.value)
     finally:
         prover.lib.cp_free(out)
+
+
+def stark_prove_batch(prover, desc, traces, challengers, publics=None, globals_=None, pow_overrides=None):
+    """cp_stark_prove_batch: traces = B host arrays (n_trace_columns, n) of ONE description -> list of B proof bytes, instance i the
+    bytes stark_prove gives for traces[i] and challengers[i] alone. publics / globals_: (B, n_public) / (B, n_global) or None;
+    pow_overrides: B entries, None = search a witness. Advances every ChallengerState in place; on an error none has moved."""
+    B = len(traces)
+    if len(challengers) != B or (pow_overrides is not None and len(pow_overrides) != B):
+        raise ValueError("one challenger (and one pow override entry) per trace")
+    ts = [_as_u64(t) for t in traces]
+    tp = (_vp * max(B, 1))(*[t.ctypes.data for t in ts])
+    (pp, gp), keep = zip(*[_opt_u64(x) for x in (publics, globals_)])
+    ch = (ChallengerState * max(B, 1))()
+    for i, c in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(ch[i]), ctypes.byref(c), ctypes.sizeof(ChallengerState))
+    up = ov = None
+    if pow_overrides is not None:
+        up = (ctypes.c_int * max(B, 1))(*[0 if w is None else 1 for w in pow_overrides])
+        ov = (ctypes.c_uint64 * max(B, 1))(*[0 if w is None else int(w) for w in pow_overrides])
+    outs, lens = (ctypes.POINTER(ctypes.c_uint8) * max(B, 1))(), (ctypes.c_size_t * max(B, 1))()
+    prover._check(prover.lib.cp_stark_prove_batch(prover.ctx, ctypes.byref(desc), B, tp, 0, pp, gp, ch, up, ov, outs, lens))
+    try:
+        proofs = [ctypes.string_at(outs[i], lens[i]) for i in range(B)]
+    finally:
+        for i in range(B):
+            prover.lib.cp_free(outs[i])
+    for i, c in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(ch[i]), ctypes.sizeof(ChallengerState))
+    return proofs
 
 
 def stark_verify(desc, challenger, proof, publics=None, globals_=None):

@@ -439,15 +439,21 @@ struct KArgs {
   uint64_t *spill;               // [n_slots - n_lds][S * lanes of the grid]
   uint64_t *const *out_cols;     // map: n_out_columns column base pointers
   size_t M;                      // points (quotient: n << q; map: n rows)
-  size_t spill_stride;           // S * (point lanes of the grid, whole waves)
+  size_t spill_stride;           // instances * S * (point lanes of the grid, whole waves)
   int degree_bits, n_alphas, n_lds;
+  // Several instances of one program in one launch (blockIdx.z): instance i reads uni + i * uni_stride, cols + i * cols_stride
+  // ([B][n_columns] pointers), alphas + i * alphas_stride, weights + i * weights_stride and writes parts + i * parts_stride,
+  // out_cols + i * out_cols_stride ([B][n_out_columns] pointers). Strides in elements; a launch of one instance leaves them 0.
+  size_t uni_stride, cols_stride, alphas_stride, weights_stride, parts_stride, out_cols_stride;
 };
 
 // The bytecode, the uniform table, the column pointer table, the alphas and the weights are read at wave-uniform addresses. Read
 // through ordinary global pointers they are VECTOR loads (the kernel also stores to global memory, so the compiler may not treat
 // them as invariant): one memory round trip per interpreted instruction for the instruction word alone, another for a pointer
 // before the column load that needs it. Through the constant address space they are scalar loads (s_load: the scalar cache,
-// invariant by definition) - the kernel never writes what it reads this way.
+// invariant by definition) - the kernel never writes what it reads this way. The instance offset of a batched launch comes from
+// blockIdx.z: it is wave-uniform, added once to the table pointers before the interpreter starts (scalar arithmetic, the pointers
+// stay in scalar registers), and the loads stay scalar loads.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define AIR_CONSTANT_AS __attribute__((address_space(4)))
 #else
@@ -466,8 +472,12 @@ struct DevMem {
   size_t pos[KP], npos[KP], gid[KP];
   bool active[KP];
   int lane;
+  // this instance's tables (KArgs: base + blockIdx.z * stride)
+  const uint64_t *uni_tab, *alpha_tab;
+  const uint64_t *const *col_tab;
+  uint64_t *const *out_tab;
   __device__ __forceinline__ uint64_t code(uint32_t pc) const { return constant_as(a.code)[pc]; }
-  __device__ __forceinline__ uint64_t alpha(int c) const { return constant_as(a.alphas)[c]; }
+  __device__ __forceinline__ uint64_t alpha(int c) const { return constant_as(alpha_tab)[c]; }
   __device__ __forceinline__ Vec<KP> slot_read(uint32_t i) const {
     Vec<KP> r;
     if ((int)i < a.n_lds) for_k<KP>([&](auto k) { r.v[k] = lds[(i * KP + k) * WAVE + lane]; });
@@ -478,21 +488,21 @@ struct DevMem {
     if ((int)i < a.n_lds) for_k<KP>([&](auto k) { lds[(i * KP + k) * WAVE + lane] = v.v[k]; });
     else for_k<KP>([&](auto k) { a.spill[(size_t)(i - a.n_lds) * a.spill_stride + gid[k]] = v.v[k]; });
   }
-  __device__ __forceinline__ uint64_t uni(uint32_t i) const { return constant_as(a.uni)[i]; }
+  __device__ __forceinline__ uint64_t uni(uint32_t i) const { return constant_as(uni_tab)[i]; }
   __device__ __forceinline__ Vec<KP> local(uint32_t i) const {
-    const uint64_t *c = (const uint64_t *)constant_as(a.cols)[i];
+    const uint64_t *c = (const uint64_t *)constant_as(col_tab)[i];
     Vec<KP> r;
     for_k<KP>([&](auto k) { r.v[k] = c[pos[k]]; });
     return r;
   }
   __device__ __forceinline__ Vec<KP> next(uint32_t i) const {
-    const uint64_t *c = (const uint64_t *)constant_as(a.cols)[i];
+    const uint64_t *c = (const uint64_t *)constant_as(col_tab)[i];
     Vec<KP> r;
     for_k<KP>([&](auto k) { r.v[k] = c[npos[k]]; });
     return r;
   }
   __device__ __forceinline__ void store(uint32_t col, const Vec<KP> &v) const {
-    uint64_t *c = (uint64_t *)constant_as(a.out_cols)[col];
+    uint64_t *c = (uint64_t *)constant_as(out_tab)[col];
     for_k<KP>([&](auto k) {
       if (active[k]) c[pos[k]] = v.v[k];
     });
@@ -500,20 +510,21 @@ struct DevMem {
 };
 
 // MODE 0: quotient (points in storage order: pos = [coset block][bit-reversed row]); MODE 1: map (pos = row, natural order).
-// A lane works on KP points, 64 apart: the wave covers KP * 64 consecutive points.
+// A lane works on KP points, 64 apart: the wave covers KP * 64 consecutive points. grid = (point blocks, segments, instances).
 template <int MODE, int KP>
 __global__ __launch_bounds__(WAVE) void k_run(KArgs a) {
   extern __shared__ uint64_t lds[];
   const int lane = threadIdx.x;
-  const uint32_t seg = blockIdx.y;
-  DevMem<KP> m{lds, a, {}, {}, {}, {}, lane};
+  const uint32_t seg = blockIdx.y, inst = blockIdx.z;
+  DevMem<KP> m{lds, a, {}, {}, {}, {}, lane, a.uni + inst * a.uni_stride, a.alphas + inst * a.alphas_stride, a.cols + inst * a.cols_stride,
+               a.out_cols + inst * a.out_cols_stride};
   Selectors<KP> sel;
   for_k<KP>([&](auto k) {
     const size_t p0 = ((size_t)blockIdx.x * KP + k) * WAVE + lane;
     m.active[k] = p0 < a.M;
     const size_t pos = m.active[k] ? p0 : a.M - 1;  // idle lanes of a short grid shadow the last point (loads stay in bounds)
     m.pos[k] = pos;
-    m.gid[k] = ((size_t)seg * gridDim.x * KP + (size_t)blockIdx.x * KP + k) * WAVE + lane;
+    m.gid[k] = (((size_t)inst * gridDim.y + seg) * gridDim.x * KP + (size_t)blockIdx.x * KP + k) * WAVE + lane;
     if (MODE == 0) {
       const size_t n = (size_t)1 << a.degree_bits;
       const uint32_t q = (uint32_t)(pos & (n - 1));
@@ -531,12 +542,14 @@ __global__ __launch_bounds__(WAVE) void k_run(KArgs a) {
   Vec<KP> acc[MAX_ALPHAS];
   run_segment(constant_as(a.seg_off)[seg], constant_as(a.seg_off)[seg + 1], m, MODE == 0 ? a.n_alphas : 0, sel, acc);
   if (MODE == 0) {
+    const uint64_t *weights = a.weights + inst * a.weights_stride;
+    uint64_t *parts = a.parts + inst * a.parts_stride;
 #pragma unroll
     for (int c = 0; c < MAX_ALPHAS; c++)
       if (c < a.n_alphas) {
-        const uint64_t wgt = constant_as(a.weights)[seg * a.n_alphas + c];
+        const uint64_t wgt = constant_as(weights)[seg * a.n_alphas + c];
         for_k<KP>([&](auto k) {
-          if (m.active[k]) a.parts[((size_t)seg * a.n_alphas + c) * a.M + m.pos[k]] = gl::mul(acc[c].v[k], wgt);
+          if (m.active[k]) parts[((size_t)seg * a.n_alphas + c) * a.M + m.pos[k]] = gl::mul(acc[c].v[k], wgt);
         });
       }
   }
@@ -565,10 +578,13 @@ __global__ __launch_bounds__(256) void k_selectors(uint64_t *out, size_t M, int 
 
 // sum of the segments' parts, / Z_H (2^q distinct values: zh_inv[nat mod 2^q]), scattered to the NATURAL order the coset iNTT reads.
 // A workgroup = 64 points x 4 groups of segments (a small trace is cut into hundreds of segments: one thread per point would walk
-// them all in sequence); the four partial sums meet in LDS.
-__global__ __launch_bounds__(256) void k_finish(const uint64_t *parts, uint32_t n_segments, int n_alphas, size_t M, int log_M, int q_bits,
-                                                const uint64_t *zh_inv, uint64_t *out) {
+// them all in sequence); the four partial sums meet in LDS. grid = (point blocks, instances): instance i sums parts + i * parts_stride
+// into out + i * out_stride.
+__global__ __launch_bounds__(256) void k_finish(const uint64_t *parts, size_t parts_stride, uint32_t n_segments, int n_alphas, size_t M, int log_M,
+                                                int q_bits, const uint64_t *zh_inv, uint64_t *out, size_t out_stride) {
   __shared__ uint64_t part[MAX_ALPHAS][4][WAVE];
+  parts += blockIdx.y * parts_stride;
+  out += blockIdx.y * out_stride;
   const int lane = threadIdx.x & (WAVE - 1), grp = threadIdx.x / WAVE;
   const size_t pos = (size_t)blockIdx.x * WAVE + lane;
   const bool active = pos < M;

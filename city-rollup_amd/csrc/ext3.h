@@ -34,10 +34,12 @@ GL_HD E adjugate_row(uint64_t m0, uint64_t m1, const E &a, uint64_t &norm) {
 
 constexpr int GROUP = 8;  // elements per lane and field inversion (16 spills: 3 x 16 adjugate rows + norms + prefixes)
 
-// lane <-> row (coalesced column accesses); blockIdx.y <-> a group of up to GROUP elements. cols: [3 * count][n]
-__global__ __launch_bounds__(256) void k_batch_inverse(uint64_t *cols, size_t count, size_t n, uint64_t m0, uint64_t m1) {
+// lane <-> row (coalesced column accesses); blockIdx.y <-> a group of up to GROUP elements. cols: [3 * count][n]; blockIdx.z <-> one
+// of several such column arrays, inst_stride elements apart
+__global__ __launch_bounds__(256) void k_batch_inverse(uint64_t *cols, size_t count, size_t n, uint64_t m0, uint64_t m1, size_t inst_stride) {
   const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (row >= n) return;
+  cols += blockIdx.z * inst_stride;
   const size_t e0 = (size_t)blockIdx.y * GROUP;
   const int g = (int)(count - e0 < (size_t)GROUP ? count - e0 : (size_t)GROUP);
   E adj[GROUP];
@@ -69,10 +71,11 @@ __global__ __launch_bounds__(256) void k_batch_inverse(uint64_t *cols, size_t co
 }
 
 // running sum of one column per workgroup: each thread sums a contiguous chunk, the 256 chunk sums are scanned in LDS, each
-// thread writes its chunk's running sums from its offset. cols: [k][n]
-__global__ __launch_bounds__(256) void k_prefix_sum(uint64_t *cols, size_t n, int exclusive) {
+// thread writes its chunk's running sums from its offset. cols: [k][n]; blockIdx.y <-> one of several such column arrays, inst_stride
+// elements apart
+__global__ __launch_bounds__(256) void k_prefix_sum(uint64_t *cols, size_t n, int exclusive, size_t inst_stride) {
   __shared__ uint64_t part[256];
-  uint64_t *col = cols + (size_t)blockIdx.x * n;
+  uint64_t *col = cols + blockIdx.y * inst_stride + (size_t)blockIdx.x * n;
   const size_t chunk = (n + 255) / 256, lo = (size_t)threadIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
   uint64_t s = 0;
   for (size_t i = lo; i < hi; i++) s = gl::add(s, col[i]);

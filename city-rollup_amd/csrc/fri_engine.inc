@@ -99,19 +99,21 @@ struct Transcript {
     h.n_out = c.n_out;
     return h;
   }
-  // one transcript (cp_fri_prove) from a state that crossed the ABI
-  int init_from(cp_ctx *ctx, const HostChallenger &c) {
-    Bn = 1;
-    device = choose_device(ctx, 1);
-    CP_TRY(arena_alloc(ctx, sizeof(tr::DevCh), (void **)&d_ch));
+  // transcripts (cp_fri_prove: one; cp_stark_prove_batch: one per instance) from states that crossed the ABI
+  int init_from(cp_ctx *ctx, const HostChallenger *c, size_t n) {
+    Bn = n;
+    device = choose_device(ctx, n);
+    CP_TRY(arena_alloc(ctx, n * sizeof(tr::DevCh), (void **)&d_ch));
     if (device) {
-      const tr::DevCh h = pack(c);
-      CP_TRY(push(ctx, d_ch, &h, sizeof h));
+      std::vector<tr::DevCh> h(n);
+      for (size_t p = 0; p < n; p++) h[p] = pack(c[p]);
+      CP_TRY(push(ctx, d_ch, h.data(), n * sizeof(tr::DevCh)));
     } else {
-      C.assign(1, c);
+      C.assign(c, c + n);
     }
     return CP_OK;
   }
+  int init_from(cp_ctx *ctx, const HostChallenger &c) { return init_from(ctx, &c, 1); }
   // host mode: the device copy of the states (the proof-of-work kernels start from it)
   int states_to_device(cp_ctx *ctx) {
     if (device) return CP_OK;

@@ -102,6 +102,19 @@ int air_uniform_table(cp_ctx *ctx, const air::Program &P, const uint64_t *public
   return CP_OK;
 }
 
+// the tables of Bn instances, [instance][uni_size]; publics / globals / challenges: [instance][n_public / n_global / n_challenge]
+int air_uniform_tables(cp_ctx *ctx, const air::Program &P, size_t Bn, const uint64_t *publics, const uint64_t *globals, const uint64_t *challenges,
+                       std::vector<uint64_t> &uni) {
+  std::vector<uint64_t> one;
+  uni.clear();
+  for (size_t i = 0; i < Bn; i++) {
+    CP_TRY(air_uniform_table(ctx, P, publics ? publics + i * P.n_public : nullptr, globals ? globals + i * P.n_global : nullptr,
+                             challenges ? challenges + i * P.n_challenge : nullptr, one));
+    uni.insert(uni.end(), one.begin(), one.end());
+  }
+  return CP_OK;
+}
+
 // how many segments a launch over `waves` waves of points is cut into: enough to fill the chip a few times over
 uint32_t air_segments_for(cp_ctx *ctx, size_t waves, size_t n_roots) {
   const size_t target = (size_t)CP_KNOB(ctx, "AIR_TARGET_WAVES", 8192);
@@ -130,7 +143,8 @@ int device_lds_per_block(cp_ctx *ctx, size_t &out) {
   return CP_OK;
 }
 
-int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::Variant &V, air::KArgs &ka, int K) {
+// one launch for Bn instances of the program (grid z; the per-instance strides of ka are the caller's)
+int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::Variant &V, air::KArgs &ka, int K, size_t Bn = 1) {
   const uint32_t S = V.C.n_segments();
   const size_t blocks = (ka.M + (size_t)air::WAVE * K - 1) / ((size_t)air::WAVE * K);
   // a slot takes K x 64 x 8 B of the workgroup's (one wave's) LDS: at most as many slots in LDS as the device grants a workgroup
@@ -142,12 +156,12 @@ int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::
   ka.code = V.d_code.get<uint64_t>();
   ka.seg_off = V.d_seg_off.get<uint32_t>();
   ka.n_lds = (int)n_lds;
-  ka.spill_stride = (size_t)S * blocks * K * air::WAVE;
+  ka.spill_stride = Bn * S * blocks * K * air::WAVE;
   ka.spill = nullptr;
   if (n_spill) CP_TRY(arena_alloc(ctx, (size_t)n_spill * ka.spill_stride * 8, (void **)&ka.spill));
   const size_t lds_bytes = (size_t)(n_lds ? n_lds : 1) * K * air::WAVE * 8;
-  if (blocks > 0x7FFFFFFFull || S > 65535) return set_error(ctx, CP_ERR_UNSUPPORTED, "AIR launch too large");
-  const dim3 grid((unsigned)blocks, S), block(air::WAVE);
+  if (blocks > 0x7FFFFFFFull || S > 65535 || Bn > 65535) return set_error(ctx, CP_ERR_UNSUPPORTED, "AIR launch too large");
+  const dim3 grid((unsigned)blocks, S, (unsigned)Bn), block(air::WAVE);
 #define CP_AIR_LAUNCH(MODE, KP) LAUNCH_LDS(ctx, name, (air::k_run<MODE, KP>), grid, block, lds_bytes, ka)
   if (map_mode) {
     if (K == 4) CP_AIR_LAUNCH(1, 4); else if (K == 2) CP_AIR_LAUNCH(1, 2); else CP_AIR_LAUNCH(1, 1);
@@ -156,6 +170,95 @@ int air_run(cp_ctx *ctx, const char *name, bool map_mode, const cp_air_program::
   }
 #undef CP_AIR_LAUNCH
   return CP_OK;
+}
+
+// The quotient chunks of Bn instances of one constraint program as COEFFICIENTS, d_q [instance][na << q][n]: the interpreter over
+// the quotient coset (one launch, the instance a grid dimension), the sum of the segments over Z_H, the coset iNTT. cols:
+// [instance][n_columns] device pointers to the committed columns on the LDE coset; uni: [instance][uni_size] (air_uniform_tables);
+// alphas: [instance][na], canonical. Enqueued on the context's stream; the tables live in the caller's arena scope.
+int air_quotient_coeffs(cp_ctx *ctx, cp_air_program *prog, size_t Bn, const std::vector<const uint64_t *> &cols, int db, int q,
+                        const std::vector<uint64_t> &uni, const uint64_t *alphas, uint32_t na, uint64_t *d_q) {
+  const air::Program &P = prog->P;
+  const int log_M = db + q;
+  const size_t n = (size_t)1 << db, M = n << q;
+  // a lane takes several points once the traces alone give every SIMD a few waves' worth of them
+  int K = air_prefetch() ? 1 : air_points_per_lane(ctx);
+  while (K > 1 && Bn * M < (size_t)air::WAVE * K * 64) K >>= 1;
+  const uint32_t want = air_segments_for(ctx, Bn * ((M + (size_t)air::WAVE * K - 1) / ((size_t)air::WAVE * K)), P.roots.size());
+  const cp_air_program::Variant *V = nullptr;
+  CP_TRY(air_variant(ctx, prog, want, &V));
+  const uint32_t S = V->C.n_segments();
+  // host-side tables: segment weights alpha^(sinks after the segment) per instance, 1 / Z_H on the coset
+  std::vector<uint64_t> weights(Bn * S * na), zh_inv((size_t)1 << q);
+  for (size_t i = 0; i < Bn; i++)
+    for (uint32_t s = 0; s < S; s++)
+      for (uint32_t c = 0; c < na; c++) weights[(i * S + s) * na + c] = gl::pow(alphas[i * na + c], V->C.sinks_after[s]);
+  {
+    uint64_t wq = gl::pow(7, (gl::P - 1) >> 32);  // primitive 2^q-th root: x^n on the coset takes the values 7^n wq^c
+    for (int i = q; i < 32; i++) wq = gl::sqr(wq);
+    const uint64_t sn = gl::pow(7, n);
+    uint64_t w = 1;
+    for (size_t c = 0; c < zh_inv.size(); c++) {
+      zh_inv[c] = gl::inv(gl::sub(gl::mul(sn, w), 1));
+      w = gl::mul(w, wq);
+    }
+  }
+  air::KArgs ka{};
+  uint64_t *d_uni, *d_alphas, *d_weights, *d_zh, *d_parts;
+  const uint64_t **d_cols;
+  CP_TRY(arena_alloc(ctx, uni.size() * 8, (void **)&d_uni));
+  CP_TRY(arena_alloc(ctx, cols.size() * 8, (void **)&d_cols));
+  CP_TRY(arena_alloc(ctx, Bn * na * 8, (void **)&d_alphas));
+  CP_TRY(arena_alloc(ctx, weights.size() * 8, (void **)&d_weights));
+  CP_TRY(arena_alloc(ctx, zh_inv.size() * 8, (void **)&d_zh));
+  CP_TRY(arena_alloc(ctx, Bn * S * na * M * 8, (void **)&d_parts));
+  CP_TRY(push(ctx, d_uni, uni.data(), uni.size() * 8));
+  CP_TRY(push(ctx, d_cols, cols.data(), cols.size() * 8));
+  CP_TRY(push(ctx, d_alphas, alphas, Bn * na * 8));
+  CP_TRY(push(ctx, d_weights, weights.data(), weights.size() * 8));
+  CP_TRY(push(ctx, d_zh, zh_inv.data(), zh_inv.size() * 8));
+  const uint64_t *sel = nullptr;
+  CP_TRY(air_selectors(ctx, db, q, &sel));
+  ka.uni = d_uni; ka.cols = d_cols; ka.sel = sel; ka.alphas = d_alphas; ka.weights = d_weights; ka.parts = d_parts; ka.out_cols = nullptr;
+  ka.M = M; ka.degree_bits = db; ka.n_alphas = (int)na;
+  if (Bn > 1) {
+    ka.uni_stride = uni.size() / Bn; ka.cols_stride = P.n_columns; ka.alphas_stride = na; ka.weights_stride = (size_t)S * na;
+    ka.parts_stride = (size_t)S * na * M;
+  }
+  CP_TRY(air_run(ctx, "air_quotient", false, *V, ka, K, Bn));
+  LAUNCH(ctx, "air_finish", air::k_finish, dim3(blocks_for(M, air::WAVE), (unsigned)Bn), dim3(256), d_parts, ka.parts_stride, S, (int)na, M, log_M, q,
+         d_zh, d_q, (size_t)na * M);
+  // values on 7<omega_M>, natural order -> coefficients; the 2^q chunks of n of every challenge are consecutive
+  return cp_ntt_dev(ctx, d_q, log_M, Bn * na, M, CP_NTT_INVERSE | CP_NTT_COSET, 7);
+}
+
+// One map program on Bn column arrays that lie inst_stride elements apart (in_cols and out_cols alike): one launch. uni as above.
+int air_map_launch(cp_ctx *ctx, cp_air_program *prog, size_t Bn, const uint64_t *in_cols, uint64_t *out_cols, size_t inst_stride, size_t n,
+                   const std::vector<uint64_t> &uni) {
+  const air::Program &P = prog->P;
+  // the stores of a map program are independent roots: cut like the constraints of a quotient, so that a short trace (2^10 rows are
+  // sixteen waves) still fills the chip - as ONE segment the 912-column map of the SHA-shaped STARK was 1.24 ms of a 7 ms proof
+  const cp_air_program::Variant *V = nullptr;
+  CP_TRY(air_variant(ctx, prog, air_segments_for(ctx, Bn * ((n + air::WAVE - 1) / air::WAVE), P.roots.size()), &V));
+  std::vector<const uint64_t *> cols(Bn * P.n_columns);
+  std::vector<uint64_t *> outs(Bn * P.n_out_columns);
+  for (size_t i = 0; i < Bn; i++) {
+    for (size_t c = 0; c < P.n_columns; c++) cols[i * P.n_columns + c] = in_cols + i * inst_stride + c * n;
+    for (size_t c = 0; c < P.n_out_columns; c++) outs[i * P.n_out_columns + c] = out_cols + i * inst_stride + c * n;
+  }
+  air::KArgs ka{};
+  uint64_t *d_uni;
+  const uint64_t **d_cols;
+  uint64_t **d_outs;
+  CP_TRY(arena_alloc(ctx, uni.size() * 8, (void **)&d_uni));
+  CP_TRY(arena_alloc(ctx, (cols.size() ? cols.size() : 1) * 8, (void **)&d_cols));
+  CP_TRY(arena_alloc(ctx, (outs.size() ? outs.size() : 1) * 8, (void **)&d_outs));
+  CP_TRY(push(ctx, d_uni, uni.data(), uni.size() * 8));
+  CP_TRY(push(ctx, d_cols, cols.data(), cols.size() * 8));
+  CP_TRY(push(ctx, d_outs, outs.data(), outs.size() * 8));
+  ka.uni = d_uni; ka.cols = d_cols; ka.out_cols = d_outs; ka.M = n; ka.degree_bits = 0; ka.n_alphas = 0;
+  if (Bn > 1) { ka.uni_stride = uni.size() / Bn; ka.cols_stride = P.n_columns; ka.out_cols_stride = P.n_out_columns; }
+  return air_run(ctx, "air_map", true, *V, ka, 1, Bn);
 }
 
 // the raw program on one row over F_p^2 (a verifier at zeta): values of every op
@@ -249,6 +352,185 @@ ZetaSelectors zeta_selectors(gl::Ext zeta, int db) {
   z.l_first = gl::ext_mul(gl::ext_scale(z.zh, n_inv), host_ext_inv(gl::ext_sub(zeta, gl::Ext{1, 0})));
   z.l_last = gl::ext_mul(gl::ext_scale(z.zh, gl::mul(n_inv, g_last)), host_ext_inv(z.z_last));
   return z;
+}
+
+// ---- cp_stark_prove_batch: Bn instances of one description through shared launches ----
+struct StarkBatchOut {
+  std::vector<ByteBuf> proofs;
+  std::vector<cp_challenger_state> challengers;
+};
+
+// The sequence of cp_stark_prove with the instance as the outer dimension of every array and a grid dimension of every launch. The
+// transcripts up to the openings are host sponges (as in cp_stark_prove: one download per round serves all of them), the FRI part
+// follows the context's transcript mode. vals: [instance][k0 + k1][n], the traces in place. Arguments are validated by the caller.
+int stark_prove_batch_impl(cp_ctx *ctx, const cp_stark_desc *desc, const StarkShape &s, size_t Bn, uint64_t *vals, const uint64_t *publics,
+                           const uint64_t *globals, const cp_challenger_state *ch_in, const int *use_pow, const uint64_t *pow_ov, StarkBatchOut &out) {
+  const size_t n = s.n, N = n << s.rb, cap_w = (size_t)4 << s.ch, inst = s.kt * n;
+  const unsigned Bu = (unsigned)Bn;
+  std::vector<HostChallenger> C(Bn);
+  for (size_t i = 0; i < Bn; i++) challenger_load(C[i], ch_in[i]);
+  // one commitment round: the k columns of every instance -> internal arrays [instance][k][...], one iNTT, one LDE, Bn trees in one
+  // Merkle call, one download of the Bn caps, which every instance's sponge then observes
+  auto commit = [&](DevBatch &O, size_t k, const uint64_t *values /* first instance's columns inside vals, or null: O.coeffs is filled */) -> int {
+    if (values) {
+      for (size_t i = 0; i < Bn; i++) CP_TRY(cp_d2d(ctx, O.coeffs + i * O.coeffs_stride, values + i * inst, k * n * 8));
+      CP_TRY(cp_ntt_dev(ctx, O.coeffs, s.db, Bn * k, n, CP_NTT_INVERSE, 0));
+    }
+    CP_TRY(cp_lde_dev(ctx, O.coeffs, n, s.db, s.rb, Bn * k, 7, CP_NTT_BITREV_OUT, O.lde, N));
+    CP_TRY(merkle_cols_batch(ctx, O.lde, N, k, N, Bn, k * N, s.ch, O.digests, O.cap));
+    CP_TRY(batch_fetch_caps(ctx, O, Bn, s.ch));
+    for (uint64_t v : O.cap_host)
+      if (v >= gl::P) return set_error(ctx, CP_ERR_INTERNAL, "non-canonical cap element");
+    for (size_t i = 0; i < Bn; i++) C[i].observe(O.cap_host.data() + i * cap_w, cap_w);
+    return CP_OK;
+  };
+  host_phase(ctx, "stark_trace");
+  DevBatch t0, t1, qb;
+  CP_TRY(batch_alloc(ctx, t0, Bn, s.k0, n, N, s.ch));
+  CP_TRY(commit(t0, s.k0, vals));
+  if (canonical_check_failed(ctx)) return CP_ERR_INVALID_ARG;  // the caller names the instance
+  std::vector<uint64_t> rch(Bn * desc->n_round_challenges);
+  if (s.k1) {
+    host_phase(ctx, "stark_extended");
+    for (size_t i = 0; i < rch.size(); i++) rch[i] = C[i / desc->n_round_challenges].challenge();
+    uint64_t *ext = vals + s.k0 * n;
+    for (size_t i = 0; i < desc->n_steps; i++) {
+      const cp_stark_step &st = desc->steps[i];
+      if (st.kind == CP_STARK_STEP_MAP) {
+        cp_air_program *prog = const_cast<cp_air_program *>(st.program);
+        if (prog->device != ctx->device) return set_error(ctx, CP_ERR_INVALID_ARG, "step %zu: the program belongs to another device", i);
+        std::vector<uint64_t> uni;
+        CP_TRY(air_uniform_tables(ctx, prog->P, Bn, publics, globals, rch.data(), uni));
+        CP_TRY(air_map_launch(ctx, prog, Bn, vals, ext, inst, n, uni));
+      } else if (st.kind == CP_STARK_STEP_CUBIC_INVERSE) {
+        const size_t groups = ((size_t)st.count + ext3::GROUP - 1) / ext3::GROUP;
+        if (groups > 65535 || n > ((size_t)1 << 32)) return set_error(ctx, CP_ERR_INVALID_ARG, "step %zu: too many elements per call", i);
+        if (st.count)
+          LAUNCH(ctx, "cubic_batch_inverse", ext3::k_batch_inverse, dim3(blocks_for(n, 256), (unsigned)groups, Bu), dim3(256), ext + (size_t)st.first * n,
+                 (size_t)st.count, n, st.modulus[0], st.modulus[1], inst);
+      } else if (st.count) {
+        LAUNCH(ctx, "column_prefix_sum", ext3::k_prefix_sum, dim3(st.count, Bu), dim3(256), ext + (size_t)st.first * n, n, (int)(st.flags & 1), inst);
+      }
+    }
+    CP_TRY(batch_alloc(ctx, t1, Bn, s.k1, n, N, s.ch));
+    CP_TRY(commit(t1, s.k1, ext));
+  }
+  host_phase(ctx, "stark_quotient");
+  std::vector<uint64_t> alphas(Bn * s.na);
+  for (size_t i = 0; i < alphas.size(); i++) alphas[i] = C[i / s.na].challenge();
+  {
+    cp_air_program *prog = const_cast<cp_air_program *>(desc->constraints);  // the cache of compiled forms is behind its mutex
+    if (prog->device != ctx->device) return set_error(ctx, CP_ERR_INVALID_ARG, "the constraints program belongs to another device");
+    std::vector<uint64_t> uni;
+    CP_TRY(air_uniform_tables(ctx, prog->P, Bn, publics, globals, rch.data(), uni));
+    std::vector<const uint64_t *> cols;
+    for (size_t i = 0; i < Bn; i++) {
+      for (size_t j = 0; j < s.k0; j++) cols.push_back(t0.lde + i * t0.lde_stride + j * N);
+      for (size_t j = 0; j < s.k1; j++) cols.push_back(t1.lde + i * t1.lde_stride + j * N);
+    }
+    CP_TRY(batch_alloc(ctx, qb, Bn, s.kq, n, N, s.ch));
+    CP_TRY(air_quotient_coeffs(ctx, prog, Bn, cols, s.db, s.q, uni, alphas.data(), s.na, qb.coeffs));
+    CP_TRY(commit(qb, s.kq, nullptr));
+  }
+  host_phase(ctx, "stark_openings");
+  // zeta and g zeta of every instance, then their inverses: [2 Bn points | 2 Bn inverses], the order fri_prove_impl reads them in
+  uint64_t g = gl::pow(7, (gl::P - 1) >> 32);
+  for (int i = s.db; i < 32; i++) g = gl::sqr(g);
+  std::vector<gl::Ext> pts(4 * Bn);
+  for (size_t i = 0; i < Bn; i++) {
+    const uint64_t za = C[i].challenge(), zb = C[i].challenge();
+    const gl::Ext z{za, zb}, zn = host_ext_pow(z, n);
+    if (zn.a == 1 && zn.b == 0)
+      return set_error(ctx, CP_ERR_INTERNAL, "instance %zu: zeta fell into the trace domain (probability 2^-%d): retry with another transcript", i, 128 - s.db);
+    // what cp_fri_prove refuses of an opening point: zero, or a point of the LDE coset (z^n != 1 leaves only these)
+    if ((z.a == 0 && z.b == 0) || (z.b == 0 && gl::pow(gl::mul(z.a, gl::inv(7)), (uint64_t)N) == 1))
+      return set_error(ctx, CP_ERR_INVALID_ARG, "instance %zu: the opening point is zero or lies on the LDE coset", i);
+    pts[2 * i] = z;
+    pts[2 * i + 1] = gl::Ext{gl::mul(z.a, g), gl::mul(z.b, g)};
+    pts[2 * Bn + 2 * i] = host_ext_inv(pts[2 * i]);
+    pts[2 * Bn + 2 * i + 1] = host_ext_inv(pts[2 * i + 1]);
+  }
+  // per instance [trace, extended, quotient at zeta | trace, extended at g zeta]: the order the transcript observes and the proof lists
+  const size_t open_stride = 2 * s.kt + s.kq;
+  gl::Ext *d_pts, *zpow, *d_open;
+  unsigned *d_flags;
+  CP_TRY(arena_alloc(ctx, pts.size() * 16, (void **)&d_pts));
+  CP_TRY(arena_alloc(ctx, pts.size() * n * 16, (void **)&zpow));
+  CP_TRY(arena_alloc(ctx, Bn * open_stride * 16, (void **)&d_open));
+  CP_TRY(arena_alloc(ctx, Bn * sizeof(unsigned), (void **)&d_flags));
+  CP_TRY(push(ctx, d_pts, pts.data(), pts.size() * 16));
+  HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, Bn * sizeof(unsigned), ctx->stream));
+  LAUNCH(ctx, "fri_ext_powers", fri::k_ext_powers, dim3(blocks_for(n, 256), 4 * Bu), dim3(256), d_pts, n, zpow);
+  auto open_at = [&](const DevBatch &O, const gl::Ext *zp, size_t at) -> int {
+    if (!O.k) return CP_OK;
+    LAUNCH(ctx, "eval_at_point", fri::k_eval_at_point, dim3((unsigned)O.k, Bu), dim3(256), O.coeffs, O.coeffs_stride, (const uint64_t *const *)nullptr, n, zp,
+           2 * n, d_open, open_stride, at);
+    return CP_OK;
+  };
+  CP_TRY(open_at(t0, zpow, 0));
+  CP_TRY(open_at(t1, zpow, s.k0));
+  CP_TRY(open_at(qb, zpow, s.kt));
+  CP_TRY(open_at(t0, zpow + n, s.kt + s.kq));
+  CP_TRY(open_at(t1, zpow + n, s.kt + s.kq + s.k0));
+  std::vector<uint64_t> open(Bn * open_stride * 2);
+  CP_TRY(fetch(ctx, open.data(), d_open, open.size() * 8));
+  for (size_t i = 0; i < Bn; i++) C[i].observe(open.data() + i * open_stride * 2, open_stride * 2);
+  // ---- prove_openings: the zeta batch over every oracle, the g zeta batch over the trace rounds ----
+  std::vector<OracleRef> oracles;
+  for (const DevBatch *O : {&t0, &t1, &qb}) {
+    if (!O->k) continue;
+    OracleRef R;
+    R.k = O->k;
+    R.coeffs = O->coeffs; R.lde = O->lde; R.digests = O->digests;
+    R.coeffs_stride = O->coeffs_stride; R.lde_stride = O->lde_stride; R.dig_stride = O->dig_stride;
+    oracles.push_back(R);
+  }
+  std::vector<FriBatchDesc> fb(2);
+  for (uint32_t o = 0; o < oracles.size(); o++) {
+    fb[0].ranges.push_back({o, 0, (uint32_t)oracles[o].k});
+    fb[0].n_polys += oracles[o].k;
+    if (o + 1 < oracles.size()) {
+      fb[1].ranges.push_back({o, 0, (uint32_t)oracles[o].k});
+      fb[1].n_polys += oracles[o].k;
+    }
+  }
+  FriCfg cfg;
+  CP_TRY(load_fri_cfg(ctx, &desc->fri, cfg));
+  Transcript T;
+  CP_TRY(T.init_from(ctx, C.data(), Bn));
+  FriHostOut fo;
+  CP_TRY(fri_prove_impl(ctx, Bn, s.db, cfg, oracles, fb, zpow, zpow + 2 * Bn * n, T, tr::Seg{nullptr, nullptr, 0, 0}, use_pow, pow_ov, d_flags, fo));
+  std::vector<tr::DevCh> hch(Bn);
+  if (T.device) CP_TRY(fetch_async(ctx, hch.data(), T.d_ch, Bn * sizeof(tr::DevCh)));
+  host_phase(ctx, "drain");
+  CP_TRY(fetch_flush(ctx));
+  CP_TRY(fo.check(ctx));
+  host_phase(ctx, "copy_out");
+  out.proofs.assign(Bn, ByteBuf());
+  out.challengers.assign(Bn, cp_challenger_state());
+  const size_t n_tr = s.k1 ? 2 : 1;
+  for (size_t i = 0; i < Bn; i++) {
+    ByteBuf &b = out.proofs[i];
+    const uint64_t *o = open.data() + i * open_stride * 2;
+    b.u64(n_tr);
+    b.u64((uint64_t)1 << s.ch); b.felts(t0.cap_host.data() + i * cap_w, cap_w);
+    if (s.k1) { b.u64((uint64_t)1 << s.ch); b.felts(t1.cap_host.data() + i * cap_w, cap_w); }
+    b.u64((uint64_t)1 << s.ch); b.felts(qb.cap_host.data() + i * cap_w, cap_w);
+    b.u64(s.kt); b.felts(o, 2 * s.kt);
+    b.u64(s.kt); b.felts(o + 2 * (s.kt + s.kq), 2 * s.kt);
+    b.u64(s.kq); b.felts(o + 2 * s.kt, 2 * s.kq);
+    fo.bytes(i, b);
+    if (!T.device) hch[i] = Transcript::pack(T.C[i]);
+    cp_challenger_state &c = out.challengers[i];
+    memset(&c, 0, sizeof c);
+    memcpy(c.sponge_state, hch[i].state, sizeof hch[i].state);
+    memcpy(c.input_buffer, hch[i].in, (size_t)hch[i].n_in * 8);
+    memcpy(c.output_buffer, hch[i].state, (size_t)hch[i].n_out * 8);
+    c.n_input = (uint32_t)hch[i].n_in;
+    c.n_output = (uint32_t)hch[i].n_out;
+  }
+  host_phase(ctx, nullptr);
+  return CP_OK;
 }
 
 }  // namespace
@@ -349,59 +631,17 @@ int cp_air_quotient_commit(cp_ctx *ctx, const cp_air_program *program, cp_poly_b
   if (P.max_degree > (1u << q) + 1) return set_error(ctx, CP_ERR_INVALID_ARG, "constraint degree %u exceeds 2^quotient_degree_bits + 1 = %u", P.max_degree, (1u << q) + 1);
   std::vector<uint64_t> uni;
   CP_TRY(air_uniform_table(ctx, P, publics, globals, challenges, uni));
-  const int log_M = db + q;
-  const size_t n = (size_t)1 << db, M = n << q, N = n << rb;
-  // a lane takes several points once the trace alone gives every SIMD a few waves' worth of them
-  int K = air_prefetch() ? 1 : air_points_per_lane(ctx);
-  while (K > 1 && M < (size_t)air::WAVE * K * 64) K >>= 1;
-  const uint32_t want = air_segments_for(ctx, (M + (size_t)air::WAVE * K - 1) / ((size_t)air::WAVE * K), P.roots.size());
-  const cp_air_program::Variant *V = nullptr;
-  CP_TRY(air_variant(ctx, prog, want, &V));
-  const uint32_t S = V->C.n_segments(), na = (uint32_t)n_alphas;
-  // host-side tables: column pointers, segment weights alpha^(sinks after the segment), 1 / Z_H on the coset
+  const size_t n = (size_t)1 << db, N = n << rb;
   std::vector<const uint64_t *> cols;
   for (size_t o = 0; o < n_oracles; o++)
     for (size_t j = 0; j < oracles[o]->k; j++) cols.push_back(oracles[o]->lde + j * N);
-  std::vector<uint64_t> weights((size_t)S * na), zh_inv((size_t)1 << q);
-  for (uint32_t s = 0; s < S; s++)
-    for (uint32_t c = 0; c < na; c++) weights[(size_t)s * na + c] = gl::pow(alphas[c], V->C.sinks_after[s]);
-  {
-    uint64_t wq = gl::pow(7, (gl::P - 1) >> 32);  // primitive 2^q-th root: x^n on the coset takes the values 7^n wq^c
-    for (int i = q; i < 32; i++) wq = gl::sqr(wq);
-    const uint64_t sn = gl::pow(7, n);
-    uint64_t w = 1;
-    for (size_t c = 0; c < zh_inv.size(); c++) {
-      zh_inv[c] = gl::inv(gl::sub(gl::mul(sn, w), 1));
-      w = gl::mul(w, wq);
-    }
-  }
   ArenaScope arena_scope(ctx, ctx->arena.used == 0);
   host_phase(ctx, "air_quotient");
-  air::KArgs ka{};
-  uint64_t *d_uni, *d_alphas, *d_weights, *d_zh, *d_parts, *d_q;
-  const uint64_t **d_cols;
-  CP_TRY(arena_alloc(ctx, uni.size() * 8, (void **)&d_uni));
-  CP_TRY(arena_alloc(ctx, cols.size() * 8, (void **)&d_cols));
-  CP_TRY(arena_alloc(ctx, na * 8, (void **)&d_alphas));
-  CP_TRY(arena_alloc(ctx, weights.size() * 8, (void **)&d_weights));
-  CP_TRY(arena_alloc(ctx, zh_inv.size() * 8, (void **)&d_zh));
-  CP_TRY(arena_alloc(ctx, (size_t)S * na * M * 8, (void **)&d_parts));
-  CP_TRY(arena_alloc(ctx, (size_t)na * M * 8, (void **)&d_q));
-  CP_TRY(push(ctx, d_uni, uni.data(), uni.size() * 8));
-  CP_TRY(push(ctx, d_cols, cols.data(), cols.size() * 8));
-  CP_TRY(push(ctx, d_alphas, alphas, na * 8));
-  CP_TRY(push(ctx, d_weights, weights.data(), weights.size() * 8));
-  CP_TRY(push(ctx, d_zh, zh_inv.data(), zh_inv.size() * 8));
-  const uint64_t *sel = nullptr;
-  CP_TRY(air_selectors(ctx, db, q, &sel));
-  ka.uni = d_uni; ka.cols = d_cols; ka.sel = sel; ka.alphas = d_alphas; ka.weights = d_weights; ka.parts = d_parts; ka.out_cols = nullptr;
-  ka.M = M; ka.degree_bits = db; ka.n_alphas = (int)na;
-  CP_TRY(air_run(ctx, "air_quotient", false, *V, ka, K));
-  LAUNCH(ctx, "air_finish", air::k_finish, dim3(blocks_for(M, air::WAVE)), dim3(256), d_parts, S, (int)na, M, log_M, q, d_zh, d_q);
-  // values on 7<omega_M>, natural order -> coefficients; the 2^q chunks of n of every challenge are consecutive
-  CP_TRY(cp_ntt_dev(ctx, d_q, log_M, na, M, CP_NTT_INVERSE | CP_NTT_COSET, 7));
+  uint64_t *d_q;
+  CP_TRY(arena_alloc(ctx, (n_alphas << q) * n * 8, (void **)&d_q));
+  CP_TRY(air_quotient_coeffs(ctx, prog, 1, cols, db, q, uni, alphas, (uint32_t)n_alphas, d_q));
   host_phase(ctx, nullptr);
-  return poly_batch_commit(ctx, d_q, true, (size_t)na << q, db, rb, ch, CP_BATCH_FROM_COEFFS, nullptr, quotient_out);
+  return poly_batch_commit(ctx, d_q, true, n_alphas << q, db, rb, ch, CP_BATCH_FROM_COEFFS, nullptr, quotient_out);
 } CP_CATCH(ctx)
 
 int cp_air_map_dev(cp_ctx *ctx, const cp_air_program *program, const uint64_t *in_cols_dev, uint64_t *out_cols_dev, size_t n, const uint64_t *publics,
@@ -416,27 +656,8 @@ int cp_air_map_dev(cp_ctx *ctx, const cp_air_program *program, const uint64_t *i
   if ((P.n_columns && !in_cols_dev) || (P.n_out_columns && !out_cols_dev)) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL column arrays");
   std::vector<uint64_t> uni;
   CP_TRY(air_uniform_table(ctx, P, publics, globals, challenges, uni));
-  // the stores of a map program are independent roots: cut like the constraints of a quotient, so that a short trace (2^10 rows are
-  // sixteen waves) still fills the chip - as ONE segment the 912-column map of the SHA-shaped STARK was 1.24 ms of a 7 ms proof
-  const cp_air_program::Variant *V = nullptr;
-  CP_TRY(air_variant(ctx, prog, air_segments_for(ctx, (n + air::WAVE - 1) / air::WAVE, P.roots.size()), &V));
-  std::vector<const uint64_t *> cols(P.n_columns);
-  std::vector<uint64_t *> outs(P.n_out_columns);
-  for (size_t c = 0; c < cols.size(); c++) cols[c] = in_cols_dev + c * n;
-  for (size_t c = 0; c < outs.size(); c++) outs[c] = out_cols_dev + c * n;
   ArenaScope arena_scope(ctx, ctx->arena.used == 0);
-  air::KArgs ka{};
-  uint64_t *d_uni;
-  const uint64_t **d_cols;
-  uint64_t **d_outs;
-  CP_TRY(arena_alloc(ctx, uni.size() * 8, (void **)&d_uni));
-  CP_TRY(arena_alloc(ctx, (cols.size() ? cols.size() : 1) * 8, (void **)&d_cols));
-  CP_TRY(arena_alloc(ctx, (outs.size() ? outs.size() : 1) * 8, (void **)&d_outs));
-  CP_TRY(push(ctx, d_uni, uni.data(), uni.size() * 8));
-  CP_TRY(push(ctx, d_cols, cols.data(), cols.size() * 8));
-  CP_TRY(push(ctx, d_outs, outs.data(), outs.size() * 8));
-  ka.uni = d_uni; ka.cols = d_cols; ka.out_cols = d_outs; ka.M = n; ka.degree_bits = 0; ka.n_alphas = 0;
-  CP_TRY(air_run(ctx, "air_map", true, *V, ka, 1));
+  CP_TRY(air_map_launch(ctx, prog, 1, in_cols_dev, out_cols_dev, 0, n, uni));
   HIP_TRY(ctx, sync_stream(ctx));
   return CP_OK;
 } CP_CATCH(ctx)
@@ -448,7 +669,7 @@ int cp_cubic_batch_inverse_dev(cp_ctx *ctx, const uint64_t modulus[2], uint64_t 
   if (modulus[0] >= gl::P || modulus[1] >= gl::P) return set_error(ctx, CP_ERR_INVALID_ARG, "modulus is not canonical");
   const size_t groups = (count + ext3::GROUP - 1) / ext3::GROUP;
   if (groups > 65535 || n > ((size_t)1 << 32)) return set_error(ctx, CP_ERR_INVALID_ARG, "too many elements per call");
-  LAUNCH(ctx, "cubic_batch_inverse", ext3::k_batch_inverse, dim3(blocks_for(n, 256), (unsigned)groups), dim3(256), cols_dev, count, n, modulus[0], modulus[1]);
+  LAUNCH(ctx, "cubic_batch_inverse", ext3::k_batch_inverse, dim3(blocks_for(n, 256), (unsigned)groups), dim3(256), cols_dev, count, n, modulus[0], modulus[1], (size_t)0);
   HIP_TRY(ctx, sync_stream(ctx));
   return CP_OK;
 } CP_CATCH(ctx)
@@ -458,7 +679,7 @@ int cp_column_prefix_sum_dev(cp_ctx *ctx, uint64_t *cols_dev, size_t k, size_t n
   if (k == 0 || n == 0) return CP_OK;
   if (!cols_dev) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL argument");
   if (k > 0x7FFFFFFFull) return set_error(ctx, CP_ERR_INVALID_ARG, "too many columns per call");
-  LAUNCH(ctx, "column_prefix_sum", ext3::k_prefix_sum, dim3((unsigned)k), dim3(256), cols_dev, n, exclusive ? 1 : 0);
+  LAUNCH(ctx, "column_prefix_sum", ext3::k_prefix_sum, dim3((unsigned)k), dim3(256), cols_dev, n, exclusive ? 1 : 0, (size_t)0);
   HIP_TRY(ctx, sync_stream(ctx));
   return CP_OK;
 } CP_CATCH(ctx)
@@ -561,6 +782,74 @@ int cp_stark_prove(cp_ctx *ctx, const cp_stark_desc *desc, const uint64_t *trace
   *proof_len = b.size();
   *challenger = ch;
   own.vals_buf.mark_idle();  // cp_fri_prove drained the stream and nothing was enqueued since
+  return CP_OK;
+} CP_CATCH(ctx)
+
+int cp_stark_prove_batch(cp_ctx *ctx, const cp_stark_desc *desc, size_t n_traces, const uint64_t *const *trace_values, int trace_on_device,
+                         const uint64_t *publics, const uint64_t *globals, cp_challenger_state *challengers, const int *use_pow_override,
+                         const uint64_t *pow_override, uint8_t **proofs_out, size_t *proof_lens) try {
+  // every argument of every instance is checked before anything is staged; nothing of the caller's is written before the last step
+  if (n_traces < 1 || n_traces > CP_STARK_BATCH_MAX) return set_error(ctx, CP_ERR_INVALID_ARG, "n_traces %zu out of range [1, %d]", n_traces, CP_STARK_BATCH_MAX);
+  if (!trace_values || !challengers || !proofs_out || !proof_lens) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL argument");
+  CHECK_CTX(ctx);
+  StarkShape s;
+  CP_TRY(stark_shape(ctx, desc, true, s));
+  const size_t Bn = n_traces;
+  if (Bn * std::max({s.k0, s.k1, s.kq}) > 65535)
+    return set_error(ctx, CP_ERR_INVALID_ARG, "%zu traces of %zu columns: more than 65535 polynomials in one launch", Bn, std::max({s.k0, s.k1, s.kq}));
+  if ((desc->n_public && !publics) || (desc->n_global && !globals)) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL publics / globals");
+  std::vector<int> up(Bn, 0);
+  std::vector<uint64_t> ov(Bn, 0);
+  for (size_t i = 0; i < Bn; i++) {
+    if (!trace_values[i]) return set_error(ctx, CP_ERR_INVALID_ARG, "instance %zu: trace_values is NULL", i);
+    if (!all_canonical(publics ? publics + i * desc->n_public : nullptr, desc->n_public) ||
+        !all_canonical(globals ? globals + i * desc->n_global : nullptr, desc->n_global))
+      return set_error(ctx, CP_ERR_INVALID_ARG, "instance %zu: a public input / global value is not canonical", i);
+    if (const char *why = challenger_problem(&challengers[i])) return set_error(ctx, CP_ERR_INVALID_ARG, "instance %zu: %s", i, why);
+    if (use_pow_override && use_pow_override[i]) {
+      if (!pow_override || pow_override[i] >= gl::P) return set_error(ctx, CP_ERR_INVALID_ARG, "instance %zu: pow witness is not canonical", i);
+      up[i] = 1;
+      ov[i] = pow_override[i];
+    }
+  }
+  StarkBatchOut out;
+  {
+    // the value columns of both trace rounds of every instance in one array: [instance][execution trace, then the extended columns][n]
+    DevBuf vals_buf = ctx->buf(DevOwn::POOLED);  // goes back as reusable only once the stream is known to be idle
+    const size_t inst = s.kt * s.n;
+    CP_TRY(alloc_status(ctx, vals_buf.alloc(Bn * inst * 8), Bn * inst * 8));
+    uint64_t *vals = vals_buf.get<uint64_t>();
+    ArenaScope arena_scope(ctx, ctx->arena.used == 0);  // drains the stream and rewinds the arena on every exit, before vals_buf goes back
+    if (s.k1) HIP_TRY(ctx, hipMemsetAsync(vals, 0, Bn * inst * 8, ctx->stream));
+    for (size_t i = 0; i < Bn; i++)
+      HIP_TRY(ctx, hipMemcpyAsync(vals + i * inst, trace_values[i], s.k0 * s.n * 8, trace_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    // host traces are scanned on the device, behind the uploads: one scan of the whole array (the extended columns are zero)
+    CP_TRY(canonical_check_enqueue(ctx, vals, trace_on_device ? 0 : Bn * inst, true));
+    const int rc = stark_prove_batch_impl(ctx, desc, s, Bn, vals, publics, globals, challengers, up.data(), ov.data(), out);
+    if (rc != CP_OK) {
+      if (!trace_on_device && canonical_check_failed(ctx)) {  // rare: find the instance and the index for the message on the host
+        for (size_t i = 0; i < Bn; i++)
+          for (size_t j = 0; j < s.k0 * s.n; j++)
+            if (trace_values[i][j] >= gl::P) return set_error(ctx, CP_ERR_INVALID_ARG, "instance %zu: trace value %zu is not canonical", i, j);
+        return set_error(ctx, CP_ERR_INVALID_ARG, "a trace value was not canonical when it was uploaded (the host array changed during the call)");
+      }
+      return rc;
+    }
+    vals_buf.mark_idle();  // the last fetch_flush drained the stream and nothing was enqueued since
+  }
+  // all or nothing: every buffer first, then the caller's arrays
+  std::vector<std::unique_ptr<uint8_t, decltype(&free)>> bufs;
+  for (size_t i = 0; i < Bn; i++) {
+    const size_t len = out.proofs[i].v.size();
+    bufs.emplace_back((uint8_t *)malloc(len ? len : 1), &free);
+    if (!bufs.back()) return set_error(ctx, CP_ERR_OOM, "out of host memory");
+    memcpy(bufs.back().get(), out.proofs[i].v.data(), len);
+  }
+  for (size_t i = 0; i < Bn; i++) {
+    proofs_out[i] = bufs[i].release();
+    proof_lens[i] = out.proofs[i].v.size();
+    challengers[i] = out.challengers[i];
+  }
   return CP_OK;
 } CP_CATCH(ctx)
 

@@ -681,6 +681,20 @@ typedef struct cp_stark_desc {
 int cp_stark_prove(cp_ctx *ctx, const cp_stark_desc *desc, const uint64_t *trace_values, int trace_on_device,
                    const uint64_t *publics, const uint64_t *globals, cp_challenger_state *challenger, int use_pow_override,
                    uint64_t pow_override, uint8_t **proof_out, size_t *proof_len);
+/* n_traces traces of ONE description in one call (the three SHA-256 STARKs of a block): instance i gets exactly the bytes and
+ * the outgoing challenger that cp_stark_prove(ctx, desc, trace_values[i], ..., &challengers[i], ...) gives, under either
+ * transcript mode, but every commitment round, every step of desc->steps, the quotient and the FRI proof are ONE set of launches
+ * for all instances. 1 <= n_traces <= CP_STARK_BATCH_MAX, and n_traces x (the widest of the three oracles) <= 65535.
+ * trace_values: n_traces pointers (all host, or all device with trace_on_device); publics / globals: n_traces x n_public /
+ * n_global (NULL when 0); challengers: n_traces, in and out; use_pow_override / pow_override: n_traces each, or NULL = no
+ * injected witness; proofs_out / proof_lens: n_traces each (malloc'd; cp_free). All or nothing: every argument of every
+ * instance is checked before anything is staged (the message names the instance), and on ANY failure - a refused argument, a
+ * trace element >= p found by the device scan, a refused allocation (CP_ERR_OOM), zeta in the trace domain - no challenger is
+ * modified, no output pointer is written, nothing is leaked and the context stays usable. */
+#define CP_STARK_BATCH_MAX 64
+int cp_stark_prove_batch(cp_ctx *ctx, const cp_stark_desc *desc, size_t n_traces, const uint64_t *const *trace_values,
+                         int trace_on_device, const uint64_t *publics, const uint64_t *globals, cp_challenger_state *challengers,
+                         const int *use_pow_override, const uint64_t *pow_override, uint8_t **proofs_out, size_t *proof_lens);
 /* The verifier (host arithmetic only; desc->steps is not read, and the program handle is used for its host form only):
  * transcript, constraints at zeta from the openings against Z_H(zeta) * sum_i zeta^(n i) t_i(zeta), then `verify_fri_proof`.
  * 0 = accepted; CP_ERR_VERIFY with cp_last_error(NULL) naming the first failing check. */

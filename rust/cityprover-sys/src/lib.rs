@@ -494,3 +494,26 @@ pub fn air_quotient_commit(ctx: &Context, program: &AirProgram, oracles: &[&Poly
     let first = oracles[0];
     Ok(PolyBatch { raw, k: alphas.len() << quotient_degree_bits, degree_bits: first.degree_bits, rate_bits: first.rate_bits, cap_height: first.cap_height, blinding: false })
 }
+
+/// Several traces of one `cp_stark_desc` in one call (`cp_stark_prove_batch`): instance `i` gets the bytes and the outgoing
+/// challenger `cp_stark_prove` gives for `traces[i]` alone, through shared launches. `publics` / `globals`: every instance's
+/// values in a row; `pow_witnesses[i]`: an injected proof-of-work witness or `None`. All or nothing: on an error no
+/// challenger has moved.
+pub fn stark_prove_batch(ctx: &Context, desc: &ffi::CpStarkDesc, traces: &[&[u64]], publics: &[u64], globals: &[u64], challengers: &mut [ffi::CpChallengerState], pow_witnesses: &[Option<u64>]) -> Result<Vec<Vec<u8>>> {
+    let n = traces.len();
+    if challengers.len() != n || pow_witnesses.len() != n {
+        return Err(anyhow!("stark_prove_batch: {n} traces, {} challengers, {} pow witnesses", challengers.len(), pow_witnesses.len()));
+    }
+    let ts: Vec<*const u64> = traces.iter().map(|t| t.as_ptr()).collect();
+    let up: Vec<c_int> = pow_witnesses.iter().map(|w| w.is_some() as c_int).collect();
+    let ov: Vec<u64> = pow_witnesses.iter().map(|w| w.unwrap_or(0)).collect();
+    let (mut outs, mut lens) = (vec![ptr::null_mut::<u8>(); n], vec![0usize; n]);
+    check(ctx.raw, unsafe {
+        ffi::cp_stark_prove_batch(ctx.raw, desc, n, ts.as_ptr(), 0, publics.as_ptr(), globals.as_ptr(), challengers.as_mut_ptr(), up.as_ptr(), ov.as_ptr(), outs.as_mut_ptr(), lens.as_mut_ptr())
+    })?;
+    Ok(outs.iter().zip(&lens).map(|(&p, &len)| {
+        let v = unsafe { std::slice::from_raw_parts(p, len) }.to_vec();
+        unsafe { ffi::cp_free(p.cast()) };
+        v
+    }).collect())
+}
