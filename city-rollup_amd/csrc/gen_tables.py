@@ -279,6 +279,20 @@ def main():
     out += c_array("POSEIDON_RCD", magic_pairs([(k - biasd) % P for k in RC] + [(-biasd) % P]))  # [2 * 360 ..] = no constant
     out += c_array("POSEIDON_DOMD_K", magic_pairs([(k - biasd) % P for k in DK]))
     out += c_array("POSEIDON_DOMD_LAST", magic_pairs([(k - biasd) % P for k in DLAST]))
+    # the partial rounds keep their planes in units of 2^32 (poseidon.h renorm32_d): a limb l is held as l * 2^-32 and converted by
+    # 1.5 * 2^20, which has the mantissa of 1.5 * 2^52 under the exponent field 0x413 — the bit pattern of l * 2^-32 + 1.5 * 2^20 is
+    # (0x413 * 2^52 + 2^51) + l, so these take out that pattern and are stored as the doubles 1.5 * 2^20 + half * 2^-32 (exact)
+    biasd32 = ((0x413 << 52) + (1 << 51)) * (1 + (1 << 32)) % P
+
+    def magic32_pairs(cs):
+        o = []
+        for c in cs:
+            for half in (c & 0xFFFFFFFF, c >> 32):
+                o.append(struct.unpack("<Q", struct.pack("<d", 1572864.0 + half / 4294967296.0))[0])
+        return o
+    out += "// the same for planes in units of 2^32: 1.5 * 2^20 + lo32 * 2^-32 and 1.5 * 2^20 + hi32 * 2^-32, constants minus that pattern\n"
+    out += c_array("POSEIDON_DOMD32_K", magic32_pairs([(k - biasd32) % P for k in DK]))
+    out += c_array("POSEIDON_DOMD32_LAST", magic32_pairs([(k - biasd32) % P for k in DLAST]))
     out += "// round 0 of a capacity word that is zero on entry (poseidon.h `ZERO_CAP`): (0 + RC[8 + i])^7, canonical\n"
     out += c_array("POSEIDON_CAP0_SBOX", [pow(RC[8 + i], 7, P) for i in range(4)], qualifier="constexpr")
     out += "// primitive 2^k-th roots of unity, k = 0..32 (7^((p-1)/2^k))\n"

@@ -15,7 +15,8 @@
 //     2^53; `mds_layer_d`), which beat the three 22-bit integer planes of `mds_limb` by 15 % on the whole permutation;
 //   * state is carried lazily (any u64 congruent to the value); the next round's constant is
 //     folded into the recombination, and only the final output is canonicalised;
-//   * the 22 partial rounds never leave the transformed domain of that CRT split (see `permute_until`).
+//   * the 22 partial rounds never leave the transformed domain of that CRT split (see `permute_until`), and keep their limb planes in
+//     units of 2^32, where the carry of a normalisation is one rounding instruction (`renorm32_d`: 6 operations per component, not 8).
 #pragma once
 #include "gl.h"
 #include "poseidon_tables.h"
@@ -46,6 +47,18 @@ struct Magic { double m0, m1; };
 __constant__ uint64_t d_RCD[2 * (ROUNDS * W + 1)];
 __constant__ uint64_t d_DDK[2 * PARTIAL];
 __constant__ uint64_t d_DDLAST[2 * W];
+// The partial rounds keep their planes in units of 2^32 (`renorm32_d`): a limb l arrives as l 2^-32 and is converted by 1.5 * 2^20, whose
+// mantissa is the one of 1.5 * 2^52 under another exponent field; POSEIDON_DOMD32_* are the same constants with that difference taken out.
+// DDK_HOST / DDLAST_HOST: what the form compiled here reads, and what a host uploads into d_DDK / d_DDLAST.
+#if defined(POSEIDON_RENORM_MAGIC)  // planes in units of 1 and the two-operation carry (rounds 2-4 of the build): kept for the A/B
+constexpr bool UNITS32 = false;
+static const uint64_t (&DDK_HOST)[2 * PARTIAL] = POSEIDON_DOMD_K;
+static const uint64_t (&DDLAST_HOST)[2 * W] = POSEIDON_DOMD_LAST;
+#else
+constexpr bool UNITS32 = true;
+static const uint64_t (&DDK_HOST)[2 * PARTIAL] = POSEIDON_DOMD32_K;
+static const uint64_t (&DDLAST_HOST)[2 * W] = POSEIDON_DOMD32_LAST;
+#endif
 GL_HD Magic rcd(int i) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return {__builtin_bit_cast(double, d_RCD[2 * i]), __builtin_bit_cast(double, d_RCD[2 * i + 1])};
@@ -57,14 +70,14 @@ GL_HD Magic domd_k(int i) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return {__builtin_bit_cast(double, d_DDK[2 * i]), __builtin_bit_cast(double, d_DDK[2 * i + 1])};
 #else
-  return {__builtin_bit_cast(double, POSEIDON_DOMD_K[2 * i]), __builtin_bit_cast(double, POSEIDON_DOMD_K[2 * i + 1])};
+  return {__builtin_bit_cast(double, DDK_HOST[2 * i]), __builtin_bit_cast(double, DDK_HOST[2 * i + 1])};
 #endif
 }
 GL_HD Magic domd_last(int i) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return {__builtin_bit_cast(double, d_DDLAST[2 * i]), __builtin_bit_cast(double, d_DDLAST[2 * i + 1])};
 #else
-  return {__builtin_bit_cast(double, POSEIDON_DOMD_LAST[2 * i]), __builtin_bit_cast(double, POSEIDON_DOMD_LAST[2 * i + 1])};
+  return {__builtin_bit_cast(double, DDLAST_HOST[2 * i]), __builtin_bit_cast(double, DDLAST_HOST[2 * i + 1])};
 #endif
 }
 // ---- what a caller keeps of a permutation, and what it knows of its input --------------------------------------------------
@@ -223,26 +236,34 @@ GL_HD void permute_textbook(uint64_t (&s)[W]) {
 //     4, 8, 32, 2, 2, 2), and replacing element 0 by its S-box output adds (new - z) / 4 to aa0 and ab0 and (new - z) / 2 to b0:
 //     exact quarter-integers;
 //   * limb -> integer is (limb + 1.5 * 2^52), whose mantissa holds limb + 2^51 (the offsets are taken out of the constant
-//     offline); carry extraction is (x + 1.5 * 2^84) - 1.5 * 2^84, the multiple of 2^32 nearest to x (balanced remainders).
-// Magnitudes (tests/test_hostsim.py replays them): a normalised limb is within 2^31 + 2^20 of zero; a layer multiplies by at
-// most 256 (aa), 44 (ab), 50 (b); element 0 is E0 + F0 + v0 < 350 x the layer's input; two layers after a normalisation every
-// limb is below 2^48.6 with two fractional bits — 51 of the 53 bits — and the limb -> integer conversion is good to 2^51.
+//     offline); carry extraction is (x + 1.5 * 2^84) - 1.5 * 2^84, the multiple of 2^32 nearest to x (balanced remainders);
+//   * inside `partial_rounds` both planes are kept in UNITS OF 2^32, a limb l as l 2^-32: the carry is then rint(x), one
+//     instruction, and limb -> integer is (x + 1.5 * 2^20), the same mantissa under another exponent (`renorm32_d`).
+// Magnitudes in the units of the partial rounds, 2^32 (tests/test_hostsim.py replays them in units of 1, tests/test_renorm_units.py
+// checks the normalisation in these): a normalised limb is within 2^-1 + 2^-12 of zero; a layer multiplies by at most 256 (aa),
+// 44 (ab), 50 (b); element 0 is E0 + F0 + v0 < 350 x the layer's input; a limb entering the normalisation is below 2^17.3 and
+// two layers after one every limb is below 2^16.6, with two fractional bits that now sit at 2^-33 and 2^-34 (2^-1, 2^-2 in units
+// of 1) — 51 of the 53 bits — and the limb -> integer conversion is good to 2^19. Nothing grows: the scaling moves every
+// exponent by -32 and no mantissa, the largest span between the top bit of a limb and its last fractional bit is 2^16.6 .. 2^-34,
+// the 51 bits it was in units of 1 (2^48.6 .. 2^-2), and the smallest non-zero magnitude, 2^-34, is far from the subnormals.
 // Index layout of a plane as before: [0..2] = aa, [3..5] = ab, [6..11] = b. SCALED: the input is W; else the transformed state.
 #if defined(__FAST_MATH__) || defined(__FINITE_MATH_ONLY__) && __FINITE_MATH_ONLY__
-#error "poseidon.h: the double-precision layers rely on IEEE semantics ((x + M) - M is a rounding, not x): do not build with -ffast-math"
+#error "poseidon.h: the double-precision layers rely on IEEE semantics ((x + M) - M is a rounding, not x, and rint rounds to nearest, ties to even — the carry of renorm32_d): do not build with -ffast-math"
 #endif
-template <bool SCALED>
+// OUT32: the products leave in units of 2^32 (every constant times 2^-32: only the exponents change) — the entry into `partial_rounds`
+template <bool SCALED, bool OUT32 = false>
 GL_HD void dom_mul_d(const double (&u)[W], double (&o)[W]) {
-  constexpr double A = SCALED ? 64.0 : 16.0;
+  constexpr double U = OUT32 ? 0x1p-32 : 1.0;
+  constexpr double A = (SCALED ? 64.0 : 16.0) * U;
   const double t = (u[0] + u[1] + u[2]) * A;
   o[0] = __builtin_fma(u[2], A, t);
   o[1] = __builtin_fma(u[0], A, t);
   o[2] = __builtin_fma(u[1], A, t);
-  constexpr double B1 = SCALED ? 4.0 : 1.0, B2 = SCALED ? 8.0 : 2.0, B8 = SCALED ? 32.0 : 8.0;
+  constexpr double B1 = (SCALED ? 4.0 : 1.0) * U, B2 = (SCALED ? 8.0 : 2.0) * U, B8 = (SCALED ? 32.0 : 8.0) * U;
   o[3] = __builtin_fma(u[5], B8, __builtin_fma(u[3], -B1, u[4] * -B2));
   o[4] = __builtin_fma(u[3], -B8, __builtin_fma(u[4], -B1, u[5] * -B2));
   o[5] = __builtin_fma(u[3], B2, __builtin_fma(u[4], -B8, u[5] * -B1));
-  constexpr double S = SCALED ? 2.0 : 1.0;
+  constexpr double S = (SCALED ? 2.0 : 1.0) * U;
   constexpr double c[6][6] = {{2, 1, 1, -1, -16, 4},  {-4, 2, 1, 1, -1, -16}, {16, -4, 2, 1, 1, -1},
                               {1, 16, -4, 2, 1, 1},   {-1, 1, 16, -4, 2, 1},  {-1, -1, 1, 16, -4, 2}};
 #pragma unroll
@@ -285,6 +306,22 @@ GL_HD void renorm_d(double &l, double &h) {
   const double t = (h + MAGIC) - MAGIC;       // t / 2^32 units of 2^64 == 2^32 - 1:  h <- h - t + t / 2^32,  l <- l - t / 2^32
   h = __builtin_fma(t, -(1.0 - INV), h);      // one rounding of an exactly representable result (t (1 - 2^-32) is an integer < 2^51)
   l = __builtin_fma(t, -INV, l);
+}
+// The same on planes kept in units of 2^32 (L = l 2^-32, H = h 2^-32, exact: only the exponents differ): the multiple of 2^32 nearest
+// to l is rint(L), ONE instruction (v_rndne_f64) where (x + MAGIC) - MAGIC is two — 6 operations per component instead of 8. Same
+// carries, ties included (both round to nearest-even), so the same limbs as `renorm_d`, scaled.
+GL_HD void renorm32_d(double &l, double &h) {
+  constexpr double INV = 0x1p-32;
+  const double c = __builtin_rint(l);
+  l -= c;
+  h = __builtin_fma(c, INV, h);
+  const double t = __builtin_rint(h);
+  h = __builtin_fma(t, -(1.0 - INV), h);
+  l = __builtin_fma(t, -INV, l);
+}
+// the form the partial rounds are compiled with
+GL_HD void renorm_planes_d(double &l, double &h) {
+  if (UNITS32) renorm32_d(l, h); else renorm_d(l, h);
 }
 // integer limbs |l|, |h| < 2^51 - 2^32 -> lazy u64 congruent to l + 2^32 h + c, for the constant c that `m` encodes. The bit
 // pattern of l + m.m0 is B + l + lo32(c') and that of h + m.m1 is B + h + hi32(c'), B = 0x433 * 2^52 + 2^51 being the pattern
@@ -432,9 +469,13 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
     nl = ll[0], nh = lh[0];
     dom_enter_d(ll, wl);
     dom_enter_d(lh, wh);
-    dom_mul_d<false>(wl, ol);
-    dom_mul_d<false>(wh, oh);
+    dom_mul_d<false, UNITS32>(wl, ol);
+    dom_mul_d<false, UNITS32>(wh, oh);
   }
+  // From here to the exit the planes are in units of 2^32 (UNITS32; U = 1 restores units of 1). Every operation multiplies by a
+  // compile-time constant or adds two planes, so the unit costs nothing: only where a limb of an S-box output (nl, nh: units of 1)
+  // meets a plane does its factor carry U, and `recombine_d` gets the constants of that unit (DDK_HOST / DDLAST_HOST).
+  constexpr double U = UNITS32 ? 0x1p-32 : 1.0;
   // TWO partial rounds per trip, with ONE application of the layer squared. Let W = (E, F, v) be the products at the top of round r,
   // K the scaled layer (dom_mul_d<true>), t = (1/4, 0, 0 | 1/4, 0, 0 | 1/2, 0, ...) what a change of element 0 is in the domain and
   // l = e_0 + e_3 + e_6 the functional that reads element 0 off the products. Round r: z = l W, S-box, W' = W + (new - z) t. Round r + 1
@@ -450,16 +491,16 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
   auto round = [&](int i, double (&al)[W], double (&ah)[W], double (&bl)[W], double (&bh)[W], bool normalise) {
     const double zl = al[0] + al[3] + al[6], zh = ah[0] + ah[3] + ah[6];
     // element 0 of the state: E0 + F0 + v0 + the diagonal 8 of the MDS on the previous S-box output
-    const uint64_t x = sbox_lazy(input(i, recombine_d(__builtin_fma(nl, 8.0, zl), __builtin_fma(nh, 8.0, zh), domd_k(i))));
+    const uint64_t x = sbox_lazy(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
     nl = (double)(uint32_t)x;
     nh = (double)(uint32_t)(x >> 32);
-    const double dl = nl - zl, dh = nh - zh;
+    const double dl = __builtin_fma(nl, U, -zl), dh = __builtin_fma(nh, U, -zh);
     al[0] = __builtin_fma(dl, 0.25, al[0]), ah[0] = __builtin_fma(dh, 0.25, ah[0]);
     al[3] = __builtin_fma(dl, 0.25, al[3]), ah[3] = __builtin_fma(dh, 0.25, ah[3]);
     al[6] = __builtin_fma(dl, 0.5, al[6]), ah[6] = __builtin_fma(dh, 0.5, ah[6]);
     if (normalise) {
 #pragma unroll
-      for (int k = 0; k < W; k++) renorm_d(al[k], ah[k]);
+      for (int k = 0; k < W; k++) renorm_planes_d(al[k], ah[k]);
     }
     dom_mul_d<true>(al, bl);
     dom_mul_d<true>(ah, bh);
@@ -475,7 +516,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
   double yl[W], yh[W];
   dom_leave_d(ol, yl);
   dom_leave_d(oh, yh);
-  yl[0] = __builtin_fma(nl, 8.0, yl[0]), yh[0] = __builtin_fma(nh, 8.0, yh[0]);
+  yl[0] = __builtin_fma(nl, 8.0 * U, yl[0]), yh[0] = __builtin_fma(nh, 8.0 * U, yh[0]);
 #pragma unroll
   for (int k = 0; k < W; k++) s[k] = recombine_d(yl[k], yh[k], domd_last(k));
 #else
@@ -483,26 +524,26 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
     // round i: element 0 = E0 + F0 + v0 + the diagonal 8 of the MDS on the previous S-box output
     {
       const double zl = al[0] + al[3] + al[6], zh = ah[0] + ah[3] + ah[6];
-      const uint64_t x = sbox_lazy(input(i, recombine_d(__builtin_fma(nl, 8.0, zl), __builtin_fma(nh, 8.0, zh), domd_k(i))));
+      const uint64_t x = sbox_lazy(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
       nl = (double)(uint32_t)x;
       nh = (double)(uint32_t)(x >> 32);
-      const double dl = nl - zl, dh = nh - zh;
+      const double dl = __builtin_fma(nl, U, -zl), dh = __builtin_fma(nh, U, -zh);
       al[0] = __builtin_fma(dl, 0.25, al[0]), ah[0] = __builtin_fma(dh, 0.25, ah[0]);
       al[3] = __builtin_fma(dl, 0.25, al[3]), ah[3] = __builtin_fma(dh, 0.25, ah[3]);
       al[6] = __builtin_fma(dl, 0.5, al[6]), ah[6] = __builtin_fma(dh, 0.5, ah[6]);
     }
 #pragma unroll
-    for (int k = 0; k < W; k++) renorm_d(al[k], ah[k]);
+    for (int k = 0; k < W; k++) renorm_planes_d(al[k], ah[k]);
     // round i + 1: element 0 one layer ahead, then the squared layer with the change of element 0 carried one layer on (a -> b)
     const double zl = dom_next_z(al), zh = dom_next_z(ah);
-    const uint64_t x = sbox_lazy(input(i + 1, recombine_d(__builtin_fma(nl, 8.0, zl), __builtin_fma(nh, 8.0, zh), domd_k(i + 1))));
+    const uint64_t x = sbox_lazy(input(i + 1, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i + 1))));
     nl = (double)(uint32_t)x;
     nh = (double)(uint32_t)(x >> 32);
-    dom_mul2_d(al, nl - zl, bl);
+    dom_mul2_d(al, __builtin_fma(nl, U, -zl), bl);
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(POSEIDON_INTERLEAVE_PLANES)  // the macro: A/B in tools/ubench_leaf_residency.hip
     __builtin_amdgcn_sched_barrier(0);  // one plane after the other: interleaved, the four arrays are live at once and the leaf hash (96 registers) spills
 #endif
-    dom_mul2_d(ah, nh - zh, bh);
+    dom_mul2_d(ah, __builtin_fma(nh, U, -zh), bh);
   };
   static_assert(PARTIAL % 4 == 2, "five double trips (ping-pong, nothing is copied) and a last single one");
 #pragma unroll 1
@@ -516,7 +557,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
   double yl[W], yh[W];
   dom_leave_d(wl, yl);
   dom_leave_d(wh, yh);
-  yl[0] = __builtin_fma(nl, 8.0, yl[0]), yh[0] = __builtin_fma(nh, 8.0, yh[0]);
+  yl[0] = __builtin_fma(nl, 8.0 * U, yl[0]), yh[0] = __builtin_fma(nh, 8.0 * U, yh[0]);
 #pragma unroll
   for (int k = 0; k < W; k++) s[k] = recombine_d(yl[k], yh[k], domd_last(k));
 #endif

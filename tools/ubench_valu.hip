@@ -66,6 +66,7 @@ DEF_KERNEL(k_pk_fma_f32, , asm volatile("v_pk_fma_f32 %0, %0, %0, %0" : "+v"(q[i
 DEF_KERNEL(k_pk_add_f32, , asm volatile("v_pk_add_f32 %0, %0, %0" : "+v"(q[i])))
 DEF_KERNEL(k_add_f64, , asm volatile("v_add_f64 %0, %0, %0" : "+v"(q[i])))
 DEF_KERNEL(k_mul_f64, , asm volatile("v_mul_f64 %0, %0, %0" : "+v"(q[i])))
+DEF_KERNEL(k_rndne_f64, , asm volatile("v_rndne_f64 %0, %0" : "+v"(q[i])))  // the carry of poseidon.h renorm32_d: one of these against two v_add_f64
 DEF_KERNEL(k_fmac_f64_vop2, , asm volatile("v_fmac_f64 %0, %1, %1" : "+v"(q[i]) : "v"(q[(i + 1) % CHAINS])))
 DEF_KERNEL(k_cvt_f64_u32, , asm volatile("v_cvt_f64_u32 %0, %1" : "=v"(q[i]) : "v"(a[i])))
 DEF_KERNEL(k_cvt_u32_f64, , asm volatile("v_cvt_u32_f64 %0, %1" : "=v"(a[i]) : "v"(q[i])))
@@ -109,13 +110,14 @@ int main() {
   RUN(k_and_b32_vop2, 1); RUN(k_xor_b32_vop2, 1); RUN(k_sub_u32_vop2, 1); RUN(k_lshlrev_b32_vop2, 1); RUN(k_mov_b32, 1);
   RUN(k_cndmask_vop2, 1); RUN(k_cndmask_sgpr, 1); RUN(k_add_co_vop2, 1); RUN(k_add_co_sgpr, 1); RUN(k_mul_u32_u24_vop2, 1);
   RUN(k_fma_f32_vop3, 1); RUN(k_fmac_f32_vop2, 1); RUN(k_mul_f32_vop2, 1); RUN(k_add_f32_vop2, 1); RUN(k_pk_fma_f32, 1); RUN(k_pk_add_f32, 1);
-  RUN(k_add_f64, 1); RUN(k_mul_f64, 1); RUN(k_fmac_f64_vop2, 1); RUN(k_cvt_f64_u32, 1); RUN(k_cvt_u32_f64, 1); RUN(k_add_u32_vop3_sgpr, 1);
+  RUN(k_add_f64, 1); RUN(k_mul_f64, 1); RUN(k_rndne_f64, 1); RUN(k_fmac_f64_vop2, 1); RUN(k_cvt_f64_u32, 1); RUN(k_cvt_u32_f64, 1); RUN(k_add_u32_vop3_sgpr, 1);
   RUN(k_mad_u64_u32_sgpr, 1); RUN(k_mad_nop_cnd, 2); RUN(k_snop, 1);
   for (int w : {1, 2, 4}) {  // fewer waves per SIMD
     printf("# %d wave(s) per SIMD\n", w);
     run(k_add_u32, "k_add_u32", 1, d_out, 256 * w, 256); run(k_and_or, "k_and_or", 1, d_out, 256 * w, 256);
     run(k_fma_f64, "k_fma_f64", 1, d_out, 256 * w, 256); run(k_mad_u64_u32, "k_mad_u64_u32", 1, d_out, 256 * w, 256);
     run(k_fma_f32_vop3, "k_fma_f32_vop3", 1, d_out, 256 * w, 256);
+    run(k_add_f64, "k_add_f64", 1, d_out, 256 * w, 256); run(k_rndne_f64, "k_rndne_f64", 1, d_out, 256 * w, 256);
   }
   hipFree(d_out);
   return 0;
