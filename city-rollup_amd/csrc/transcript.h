@@ -57,7 +57,11 @@ __global__ __launch_bounds__(64) void k_step(StepArgs a) {
   DevCh *c = a.ch + (active ? p : 0);
   uint64_t x = active ? c->state[ee] : 0, buf = (active && ee < 8) ? c->in[ee] : 0;
   // lockstep: the counters of this wave's first challenger are those of all five (same shape, same history); only this wave
-  // writes them
+  // writes them. INVARIANT (the callers': cp_stark_prove_batch, cp_fri_prove): every challenger that reaches the device has the
+  // same (n_in, n_out) as its neighbours. Incoming challengers may differ in how much they have absorbed; each instance draws a
+  // challenge on the host first (a duplex: n_in = 0, n_out = 7 whatever the prefix was) or is normalised to one buffer state, and
+  // from there on all instances observe and draw the same counts. tests/test_gpu_stark_batch.py (prefixes of 0 .. 13 elements in
+  // one batch) and tests/test_gpu_fri_generic.py (every incoming buffer state) pin it.
   int n_in = a.ch[(size_t)blockIdx.x * pcoop::STATES_PER_WAVE].n_in, n_out = a.ch[(size_t)blockIdx.x * pcoop::STATES_PER_WAVE].n_out;
   for (int s = 0; s < a.n_seg; s++) {
     const Seg sg = a.seg[s];

@@ -150,8 +150,9 @@ def instance_inputs(spec):
     return polys, salts
 
 
-def run_instance(be, spec, polys=None, salts=None, pow_override=None):
-    """commit -> transcript -> openings -> prove_openings on backend `be`. Returns a dict with everything a verifier needs."""
+def run_instance(be, spec, polys=None, salts=None, pow_override=None, before_prove=None):
+    """commit -> transcript -> openings -> prove_openings on backend `be`. Returns a dict with everything a verifier needs.
+    before_prove(be, challenger): further transcript traffic right before prove_openings (the buffer state it starts from)."""
     if polys is None:
         polys, salts = instance_inputs(spec)
     db, rb, ch = spec["degree_bits"], spec["rate_bits"], spec["cap_height"]
@@ -173,6 +174,8 @@ def run_instance(be, spec, polys=None, salts=None, pow_override=None):
             opened.append(np.concatenate(vals))
         for o in opened:
             be.observe(c, o)
+        if before_prove is not None:
+            before_prove(be, c)
         state_before = be.state(c)
         params = be.fri_params(db, rb, ch, spec["pow_bits"], spec["num_query_rounds"], spec["arity_bits"])
         proof = be.fri_prove(B, batches, params, c, pow_override)

@@ -1,301 +1,79 @@
 // TEST-ONLY: host-side instantiation of the __host__ __device__ arithmetic in city-rollup_amd/csrc
 // so that the exact device formulas (lazy reductions, limb MDS, shift twiddles) can be unit-tested and
-// run under sanitizers on the CPU. Never loaded by the product path.
-#include "../../city-rollup_amd/csrc/gl.h"
-#include "../../city-rollup_amd/csrc/poseidon.h"
+// run under sanitizers on the CPU. Never loaded by the product path. What each entry computes on one element is in
+// sim_gl.h / sim_bls.h, shared with the device twin of this library (tests/devsim): every arithmetic `hs_<name>` here has a
+// `ds_<name>` there (tests/test_devsim_ledger.py).
+#include "sim_gl.h"
 
 extern "C" {
 void hs_poseidon_permute(uint64_t *states, size_t n) {
-  for (size_t i = 0; i < n; i++) {
-    uint64_t s[12];
-    for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
-    poseidon::permute(s);
-    for (int k = 0; k < 12; k++) states[12 * i + k] = s[k];
-  }
+  for (size_t i = 0; i < n; i++) sim::permute(states + 12 * i, 0);
 }
 void hs_poseidon_permute_textbook(uint64_t *states, size_t n) {
-  for (size_t i = 0; i < n; i++) {
-    uint64_t s[12];
-    for (int k = 0; k < 12; k++) s[k] = states[12 * i + k];
-    poseidon::permute_textbook(s);
-    for (int k = 0; k < 12; k++) states[12 * i + k] = s[k];
-  }
+  for (size_t i = 0; i < n; i++) sim::permute(states + 12 * i, 4);
 }
 // double-precision layers (poseidon.h): carry normalisation of a two-limb value; one plane through T / K / T^-1'
-void hs_renorm_d(const double *in, double *out) {
-  out[0] = in[0], out[1] = in[1];
-  poseidon::renorm_d(out[0], out[1]);
-}
-void hs_dom_d(int op, const double *s, double *y) {  // 0: dom_enter_d, 1: dom_mul_d<false>, 2: dom_mul_d<true>, 3: dom_leave_d
-  double a[12], b[12];
-  for (int i = 0; i < 12; i++) a[i] = s[i];
-  if (op == 0) poseidon::dom_enter_d(a, b);
-  else if (op == 1) poseidon::dom_mul_d<false>(a, b);
-  else if (op == 2) poseidon::dom_mul_d<true>(a, b);
-  else poseidon::dom_leave_d(a, b);
-  for (int i = 0; i < 12; i++) y[i] = b[i];
-}
+void hs_renorm_d(const double *in, double *out) { sim::renorm(1, in, out); }
+// 0: dom_enter_d, 1: dom_mul_d<false>, 2: dom_mul_d<true>, 3: dom_leave_d; 4 .. 7: see sim::dom_d (op 6 reads a thirteenth input)
+void hs_dom_d(int op, const double *s, double *y) { sim::dom_d(op, s, y); }
 uint64_t hs_recombine_d(double l, double h, uint64_t c) {  // c: the constant already minus B (1 + 2^32), as the tables hold it
-  return poseidon::recombine_d(l, h, poseidon::Magic{0x1.8p52 + (double)(uint32_t)c, 0x1.8p52 + (double)(uint32_t)(c >> 32)});
+  return sim::recombine_const(l, h, c);
 }
-void hs_mds_layer(uint64_t *s, int which) {  // 0: integer planes (mds_layer), 1: double-precision planes (mds_layer_d); no constant
-  uint64_t t[12];
-  for (int i = 0; i < 12; i++) t[i] = s[i];
-  if (which) poseidon::mds_layer_d(t, -1); else poseidon::mds_layer(t, -1);
-  for (int i = 0; i < 12; i++) s[i] = gl::canon(t[i]);
-}
-uint64_t hs_mul(uint64_t a, uint64_t b) { return gl::mul(a, b); }
-uint64_t hs_mul_lazy(uint64_t a, uint64_t b) { return poseidon::mul_lazy(a, b); }
-uint64_t hs_add(uint64_t a, uint64_t b) { return gl::add(a, b); }
-uint64_t hs_sub(uint64_t a, uint64_t b) { return gl::sub(a, b); }
+void hs_mds_layer(uint64_t *s, int which) { sim::mds_layer(s, which); }  // 0: integer planes, 1: double-precision planes; no constant
+uint64_t hs_mul(uint64_t a, uint64_t b) { return sim::gl_op2(0, a, b); }
+uint64_t hs_mul_lazy(uint64_t a, uint64_t b) { return sim::gl_op2(1, a, b); }
+uint64_t hs_add(uint64_t a, uint64_t b) { return sim::gl_op2(2, a, b); }
+uint64_t hs_sub(uint64_t a, uint64_t b) { return sim::gl_op2(3, a, b); }
+uint64_t hs_gl_op1(int op, uint64_t a) { return sim::gl_op1(op, a); }
+uint64_t hs_gl_op2(int op, uint64_t a, uint64_t b) { return sim::gl_op2(op, a, b); }
+uint64_t hs_mul_add_lazy(uint64_t a, uint64_t b, uint64_t c) { return gl::mul_add_lazy(a, b, c); }
+uint64_t hs_fold_top(uint64_t lo, uint32_t top) { return gl::fold_top(lo, top); }
+// form 0: (lo, hi); form 1: (lo, hi', cy), given as the true high half hi = hi' + cy 2^32 and cy
+uint64_t hs_reduce128_lazy(int form, uint64_t lo, uint64_t hi, uint32_t cy) { return sim::reduce128_lazy(form, lo, hi, cy, 0); }
+void hs_ext_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) { sim::ext_mul(a, b, out); }
+void hs_gl_chain(int which, uint64_t a, uint64_t b, uint64_t c, uint64_t *out) { sim::gl_chain(which, a, b, c, out); }
 // which rare paths a * b takes in reduce128_lazy / fold_top (tests/rare_paths.py restates this with Python integers):
 // bit 0 = the borrow of `lo - w3`, bit 1 = the wrap of `+ w2 (2^32 - 1)`, bit 2 = the lazy result is >= p (canon matters)
-int hs_mul_paths(uint64_t a, uint64_t b) {
-  uint64_t lo, hi;
-  gl::mul_wide(a, b, lo, hi);
-  const uint32_t w2 = gl::lo32(hi), w3 = gl::hi32(hi);
-  const gl::u128 t = (gl::u128)lo - w3;
-  const int borrow = (uint64_t)(t >> 64) != 0;
-  const uint64_t t0 = (uint64_t)t - ((uint64_t)(t >> 64) & gl::EPS);
-  const gl::u128 s = (gl::u128)t0 + (((uint64_t)w2 << 32) - w2);
-  const int wrap = (uint64_t)(s >> 64) != 0;
-  const uint64_t lazy = gl::reduce128_lazy(lo, hi);
-  if (lazy != gl::fold_top(t0, w2)) return -1;  // the pieces above are the ones reduce128_lazy is made of
-  return borrow | wrap << 1 | (lazy >= gl::P) << 2;
-}
+int hs_mul_paths(uint64_t a, uint64_t b) { return sim::mul_paths(a, b); }
 // `permute_until` composed from the same layers, WITHOUT the final canon: the lazy state the device canonicalises on its way out
 void hs_poseidon_permute_lazy(uint64_t *states, size_t n) {
-  using namespace poseidon;
-  for (size_t i = 0; i < n; i++) {
-    uint64_t s[W];
-    for (int k = 0; k < W; k++) s[k] = add_const_lazy(states[W * i + k], rc(k));
-    for (int r = 0; r < HALF_FULL - 1; r++) {
-      for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);
-      mds_layer_d(s, (r + 1) * W);
-    }
-    for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);
-    partial_rounds(s, SameInput(), NeverStop());
-    for (int r = HALF_FULL + PARTIAL; r < ROUNDS; r++) {
-      for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);
-      mds_layer_d(s, r + 1 < ROUNDS ? (r + 1) * W : -1);
-    }
-    for (int k = 0; k < W; k++) states[W * i + k] = s[k];
-  }
+  for (size_t i = 0; i < n; i++) sim::permute(states + 12 * i, 5);
 }
-void hs_mds_limb(const uint32_t *s, uint32_t *y) {
-  uint32_t a[12], b[12];
-  for (int i = 0; i < 12; i++) a[i] = s[i];
-  poseidon::mds_limb(a, b);
-  for (int i = 0; i < 12; i++) y[i] = b[i];
-}
-}
-#include "../../city-rollup_amd/csrc/ntt16.h"
-extern "C" {
-#define MP(K) case K: return ntt16::mul_pow2<K>(x);
-uint64_t hs_mul_pow2(uint64_t x, int k) {
-  switch (k) {
-    MP(0) MP(1) MP(5) MP(12) MP(24) MP(31) MP(32) MP(33) MP(36) MP(48) MP(60) MP(63) MP(64) MP(65) MP(72) MP(84) MP(95)
-    default: return ~0ull;
-  }
-}
-void hs_round16(uint64_t *x, int inverse) {
-  uint64_t r[16];
-  for (int i = 0; i < 16; i++) r[i] = x[i];
-  if (inverse) ntt16::round16<true, 4, true>(r, 1); else ntt16::round16<false, 4, true>(r, 1);
-  for (int i = 0; i < 16; i++) x[i] = r[i];
+void hs_mds_limb(const uint32_t *s, uint32_t *y) { sim::mds_limb(s, y); }
+uint64_t hs_mul_pow2(uint64_t x, int k) { return sim::mul_pow2(x, k); }  // 0 <= k < 192 (2^96 == -1)
+void hs_round16(uint64_t *x, int inverse) { sim::round16(x, inverse); }
+// ext3.h on the host: op 0 = mul, 1 = inverse through adjugate_row / norm, 2 = mulx, 3 = adjugate_row and norm (out: 4 words)
+void hs_cubic(int op, const uint64_t *m, const uint64_t *a, const uint64_t *b, uint64_t *out) {
+  uint64_t r[4] = {0, 0, 0, 0};
+  sim::cubic(op, m, a, b, r);
+  for (int i = 0; i < (op == 3 ? 4 : 3); i++) out[i] = r[i];
 }
 }
 
-// ---- BLS12-381 (csrc/bls12_381.h) ----
-#include "../../city-rollup_amd/csrc/bls12_381.h"
+// ---- BLS12-381 (csrc/bls12_381.h, bls12_381_fr.h) and the one-limb product of r1cs.h ----
+#include "sim_bls.h"
 extern "C" {
-// canonical 12-word operands -> canonical (a*b mod p, a+b, a-b by op 0/1/2; 3: a^-1; 4: a^2 by the dedicated square)
-void hs_bls_fp_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  bls::Fp x = bls::fp_from_canonical(a), y = bls::fp_from_canonical(b), r;
-  switch (op) {
-    case 0: r = bls::fp_mul(x, y); break;
-    case 1: r = bls::fp_add(x, y); break;
-    case 2: r = bls::fp_sub(x, y); break;
-    case 4: r = bls::fp_sqr_mont(x); break;
-    default: r = bls::fp_inv(x); break;
-  }
-  bls::fp_to_canonical(r, out);
-}
-// F_p^2: 24-word operands (c0, c1); op 0 mul, 1 sqr, 2 inv
-void hs_bls_fp2_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  using F2 = bls::Field<bls::Fp2>;
-  bls::Fp2 x = F2::from_canonical(a), y = F2::from_canonical(b), r;
-  switch (op) {
-    case 0: r = bls::fp2_mul(x, y); break;
-    case 1: r = bls::fp2_sqr(x); break;
-    default: r = bls::fp2_inv(x); break;
-  }
-  F2::to_canonical(r, out);
-}
-}
-// op 0: general add (both lifted to Jacobian, p scaled to a non-trivial z first), 1: mixed add, 2: double p, 3: p * k
-template <class F>
-static int hs_group_op(int op, const uint32_t *p_xy, int p_inf, const uint32_t *q_xy, int q_inf, uint32_t k, uint32_t *out_xy) {
-  using Fd = bls::Field<F>;
-  bls::JacT<F> p = bls::jac_inf<F>(), q = bls::jac_inf<F>(), r;
-  bls::AffineT<F> qa = bls::affine_from_canonical<F>(q_xy);
-  if (!p_inf) {  // give p a z != 1 so the projective formulas are exercised: (x z^2, y z^3, z), z = 3
-    const bls::AffineT<F> pa = bls::affine_from_canonical<F>(p_xy);
-    const F z = bls::f_add(Fd::one(), bls::f_add(Fd::one(), Fd::one())), z2 = bls::f_sqr(z);
-    p = {bls::f_mul(pa.x, z2), bls::f_mul(pa.y, bls::f_mul(z2, z)), z};
-  }
-  if (!q_inf) q = {qa.x, qa.y, Fd::one()};
-  switch (op) {
-    case 0: r = bls::jac_add(p, q); break;
-    case 1: r = q_inf ? p : bls::jac_add_mixed(p, qa); break;
-    case 2: r = bls::jac_double(p); break;
-    default: r = bls::jac_mul_small(p, k); break;
-  }
-  return bls::jac_to_affine_canonical(r, out_xy) ? 1 : 0;
-}
-// the bucket accumulation on loose (bounded, unreduced) values: sum of n affine points (xy: n x 2 x WORDS canonical words,
-// none at infinity) through xyzz_add_mixed_loose, result canonical affine; returns 1 for infinity. max_bound_p (optional):
-// the largest coordinate component seen, in units of p rounded up — what LooseBound promises is checked by the caller.
-template <class F>
-static int hs_bucket_chain(const uint32_t *xy, size_t n, uint32_t *out_xy) {
-  constexpr int W = bls::Field<F>::WORDS;
-  bls::XyzzT<F> acc = bls::xyzz_inf<F>();
-  for (size_t i = 0; i < n; i++) acc = bls::xyzz_add_mixed_loose(acc, bls::affine_from_canonical<F>(xy + 2 * W * i));
-  return bls::jac_to_affine_canonical(bls::xyzz_to_jac_loose(acc), out_xy) ? 1 : 0;
-}
-extern "C" {
-int hs_bls_g1_chain(const uint32_t *xy, size_t n, uint32_t *out_xy) { return hs_bucket_chain<bls::Fp>(xy, n, out_xy); }
-int hs_bls_g2_chain(const uint32_t *xy, size_t n, uint32_t *out_xy) { return hs_bucket_chain<bls::Fp2>(xy, n, out_xy); }
-// loose field primitives against Python integers: op 0 lz_mul, 1 lz_add, 2 lz_sub<8>, 3 lz_weak<16>, 4 lz_canon; a, b: 14 raw limbs
-void hs_bls_lz_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  bls::Fp x, y, r;
-  for (int i = 0; i < bls::NL; i++) x.l[i] = a[i], y.l[i] = b[i];
-  switch (op) {
-    case 0: r = bls::lz_mul(x, y); break;
-    case 1: r = bls::lz_add(x, y); break;
-    case 2: r = bls::lz_sub<8>(x, y); break;
-    case 3: r = bls::lz_weak<16>(x); break;
-    default: r = bls::lz_canon(x); break;
-  }
-  for (int i = 0; i < bls::NL; i++) out[i] = r.l[i];
-}
-int hs_bls_lz_maybe_zero(const uint32_t *a) {
-  bls::Fp x;
-  for (int i = 0; i < bls::NL; i++) x.l[i] = a[i];
-  return bls::lz_maybe_zero(x) ? 1 : 0;
-}
-}
-// ---- what tests/bls_rare_paths.py restates, on raw limbs -------------------------------------------------------------
-#include <cstring>
-// one xyzz_add_mixed_loose: acc = x, y, zz, zzz as raw 28-bit limbs (NL per F_p component), q canonical words. Returns which
-// way the addition went, decided with the same primitives the addition itself uses:
-// 0 first point, 1 loose general, 2 doubling, 3 cancellation, 4 loose general after the filter passed on a non-zero difference
-template <class F>
-static int hs_loose_step(const uint32_t *acc_limbs, const uint32_t *q_xy, uint32_t *out_limbs) {
-  using B = bls::LooseBound<F>;
-  bls::XyzzT<F> p;
-  static_assert(sizeof(p) == 4 * sizeof(F) && sizeof(F) % sizeof(bls::Fp) == 0, "an accumulator is nothing but limbs");
-  memcpy(&p, acc_limbs, sizeof p);
-  const bls::AffineT<F> q = bls::affine_from_canonical<F>(q_xy);
-  int way = 0;
-  if (!bls::f_is_zero(p.zz)) {
-    const F pp_ = bls::lf_sub<B::X>(bls::lf_mul(q.x, p.zz), p.x);
-    const bool maybe = bls::lf_maybe_zero(pp_), zero = bls::f_is_zero(bls::lf_canon(pp_));
-    if (zero) way = bls::f_eq(bls::lf_canon(p.y), bls::f_mul(q.y, bls::lf_canon(p.zzz))) ? 2 : 3;
-    else way = maybe ? 4 : 1;
-    if (zero && !maybe) way = -1;  // the filter is a necessary condition
-  }
-  const bls::XyzzT<F> r = bls::xyzz_add_mixed_loose(p, q);
-  memcpy(out_limbs, &r, sizeof r);
-  return way;
-}
-// the accumulator as the kernels hand it on: canonical affine words; returns 1 for infinity
-template <class F>
-static int hs_loose_out(const uint32_t *acc_limbs, uint32_t *out_xy) {
-  bls::XyzzT<F> p;
-  memcpy(&p, acc_limbs, sizeof p);
-  return bls::jac_to_affine_canonical(bls::xyzz_to_jac_loose(p), out_xy) ? 1 : 0;
-}
-extern "C" {
-int hs_bls_g1_loose_step(const uint32_t *acc, const uint32_t *q_xy, uint32_t *out) { return hs_loose_step<bls::Fp>(acc, q_xy, out); }
-int hs_bls_g2_loose_step(const uint32_t *acc, const uint32_t *q_xy, uint32_t *out) { return hs_loose_step<bls::Fp2>(acc, q_xy, out); }
-int hs_bls_g1_loose_out(const uint32_t *acc, uint32_t *out_xy) { return hs_loose_out<bls::Fp>(acc, out_xy); }
-int hs_bls_g2_loose_out(const uint32_t *acc, uint32_t *out_xy) { return hs_loose_out<bls::Fp2>(acc, out_xy); }
-// raw limbs in, raw limbs out: op 0 fp_mul, 1 lz_mul, 2 lz_sqr (of a), 3 fp_sqr_mont (of a), 4 lz_add_nc
-void hs_bls_fp_raw(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  bls::Fp x, y, r;
-  for (int i = 0; i < bls::NL; i++) x.l[i] = a[i], y.l[i] = b[i];
-  switch (op) {
-    case 0: r = bls::fp_mul(x, y); break;
-    case 1: r = bls::lz_mul(x, y); break;
-    case 2: r = bls::lz_sqr(x); break;
-    case 3: r = bls::fp_sqr_mont(x); break;
-    default: r = bls::lz_add_nc(x, y); break;
-  }
-  for (int i = 0; i < bls::NL; i++) out[i] = r.l[i];
-}
-// lz_sub<K> / lz_weak<K> for every K the two accumulations use; returns -1 for any other
-#define HS_K(K) case K: r = weak ? bls::lz_weak<K>(x) : bls::lz_sub<K>(x, y); break;
-int hs_bls_lz_k(int weak, int K, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  bls::Fp x, y, r;
-  for (int i = 0; i < bls::NL; i++) x.l[i] = a[i], y.l[i] = b[i];
-  switch (K) {
-    HS_K(2) HS_K(4) HS_K(6) HS_K(8) HS_K(10) HS_K(12) HS_K(16) HS_K(18) HS_K(22)
-    default: return -1;
-  }
-  for (int i = 0; i < bls::NL; i++) out[i] = r.l[i];
-  return 0;
-}
-#undef HS_K
-}
-extern "C" {
+void hs_bls_fp_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) { sim::bls_fp_op(op, a, b, out); }
+void hs_bls_fp2_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) { sim::bls_fp2_op(op, a, b, out); }
+int hs_bls_g1_chain(const uint32_t *xy, size_t n, uint32_t *out_xy) { return sim::bucket_chain<bls::Fp>(xy, n, out_xy); }
+int hs_bls_g2_chain(const uint32_t *xy, size_t n, uint32_t *out_xy) { return sim::bucket_chain<bls::Fp2>(xy, n, out_xy); }
+void hs_bls_lz_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) { sim::bls_lz_op(op, a, b, out); }
+int hs_bls_lz_maybe_zero(const uint32_t *a) { return sim::bls_lz_maybe_zero(a); }
+int hs_bls_g1_loose_step(const uint32_t *acc, const uint32_t *q_xy, uint32_t *out) { return sim::loose_step<bls::Fp>(acc, q_xy, out); }
+int hs_bls_g2_loose_step(const uint32_t *acc, const uint32_t *q_xy, uint32_t *out) { return sim::loose_step<bls::Fp2>(acc, q_xy, out); }
+int hs_bls_g1_loose_out(const uint32_t *acc, uint32_t *out_xy) { return sim::loose_out<bls::Fp>(acc, out_xy); }
+int hs_bls_g2_loose_out(const uint32_t *acc, uint32_t *out_xy) { return sim::loose_out<bls::Fp2>(acc, out_xy); }
+void hs_bls_fp_raw(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) { sim::bls_fp_raw(op, a, b, out); }
+int hs_bls_lz_k(int weak, int K, const uint32_t *a, const uint32_t *b, uint32_t *out) { return sim::bls_lz_k(weak, K, a, b, out); }
 int hs_bls_g1_op(int op, const uint32_t *p_xy, int p_inf, const uint32_t *q_xy, int q_inf, uint32_t k, uint32_t *out_xy) {
-  return hs_group_op<bls::Fp>(op, p_xy, p_inf, q_xy, q_inf, k, out_xy);
+  return sim::group_op<bls::Fp>(op, p_xy, p_inf, q_xy, q_inf, k, out_xy);
 }
 int hs_bls_g2_op(int op, const uint32_t *p_xy, int p_inf, const uint32_t *q_xy, int q_inf, uint32_t k, uint32_t *out_xy) {
-  return hs_group_op<bls::Fp2>(op, p_xy, p_inf, q_xy, q_inf, k, out_xy);
+  return sim::group_op<bls::Fp2>(op, p_xy, p_inf, q_xy, q_inf, k, out_xy);
 }
-}
-
-// ---- BLS12-381 scalar field (csrc/bls12_381_fr.h) ----
-#include "../../city-rollup_amd/csrc/bls12_381_fr.h"
-extern "C" {
-// 8-word canonical operands; op 0 mul, 1 add, 2 sub, 3 inverse of a, 4 a^(b[0])
-void hs_bls_fr_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  blsfr::Fr x = blsfr::fr_from_canonical(a), y = blsfr::fr_from_canonical(b), r;
-  switch (op) {
-    case 0: r = blsfr::fr_mul(x, y); break;
-    case 1: r = blsfr::fr_add(x, y); break;
-    case 2: r = blsfr::fr_sub(x, y); break;
-    case 3: r = blsfr::fr_inv(x); break;
-    default: r = blsfr::fr_pow_u64(x, ((uint64_t)b[1] << 32) | b[0]); break;
-  }
-  blsfr::fr_to_canonical(r, out);
-}
-// raw limbs in, raw limbs out: op 0 fr_mul, 1 fr_add, 2 fr_sub, 3 fr_from_canonical (a: 8 words)
-void hs_bls_fr_raw(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  blsfr::Fr x = blsfr::fr_zero(), y, r;
-  if (op != 3) for (int i = 0; i < blsfr::NL; i++) x.l[i] = a[i];
-  for (int i = 0; i < blsfr::NL; i++) y.l[i] = b[i];
-  switch (op) {
-    case 0: r = blsfr::fr_mul(x, y); break;
-    case 1: r = blsfr::fr_add(x, y); break;
-    case 2: r = blsfr::fr_sub(x, y); break;
-    default: r = blsfr::fr_from_canonical(a); break;
-  }
-  for (int i = 0; i < blsfr::NL; i++) out[i] = r.l[i];
-}
-}
-
-// ---- r1cs.h: the one-limb product ----
-#include "../../city-rollup_amd/csrc/r1cs.h"
-extern "C" {
-void hs_r1cs_mul_small(const uint32_t *w, uint32_t c, uint32_t *out) {
-  blsfr::Fr x, r;
-  for (int i = 0; i < blsfr::NL; i++) x.l[i] = w[i];
-  r = r1cs::mul_small(x, c);
-  for (int i = 0; i < blsfr::NL; i++) out[i] = r.l[i];
-}
+void hs_bls_fr_op(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) { sim::bls_fr_op(op, a, b, out); }
+void hs_bls_fr_raw(int op, const uint32_t *a, const uint32_t *b, uint32_t *out) { sim::bls_fr_raw(op, a, b, out); }
+void hs_r1cs_mul_small(const uint32_t *w, uint32_t c, uint32_t *out) { sim::r1cs_mul_small(w, c, out); }
 }
 
 // ---- host_util.h: worker threads that cannot take the process down ----
@@ -495,17 +273,4 @@ int hs_air_point(int kind, const uint32_t *ops, size_t n_ops, const uint64_t *co
   info_out[0] = C.n_segments(); info_out[1] = C.n_slots; info_out[2] = (uint32_t)C.code.size(); info_out[3] = (uint32_t)P.n_live; info_out[4] = P.max_degree;
   return 0;
 }
-// ext3.h on the host: op 0 = mul, 1 = inverse through adjugate_row / norm
-void hs_cubic(int op, const uint64_t *m, const uint64_t *a, const uint64_t *b, uint64_t *out) {
-  ext3::E r;
-  if (op == 0) r = ext3::mul(m[0], m[1], ext3::E{{a[0], a[1], a[2]}}, ext3::E{{b[0], b[1], b[2]}});
-  else {
-    uint64_t norm;
-    r = ext3::adjugate_row(m[0], m[1], ext3::E{{a[0], a[1], a[2]}}, norm);
-    const uint64_t ni = norm ? gl::inv(norm) : 0;
-    for (int i = 0; i < 3; i++) r.c[i] = gl::mul(r.c[i], ni);
-  }
-  for (int i = 0; i < 3; i++) out[i] = r.c[i];
 }
-}
-

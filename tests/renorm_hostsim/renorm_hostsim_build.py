@@ -8,7 +8,7 @@ SO = os.path.join(HERE, "librenorm_hostsim.so")
 def build():
     src = os.path.join(HERE, "renorm_hostsim.hip")
     csrc = os.path.join(HERE, "..", "..", "city-rollup_amd", "csrc")
-    deps = [src] + [os.path.join(csrc, f) for f in ("poseidon.h", "poseidon_tables.h", "gl.h")]
+    deps = [src, os.path.join(HERE, "..", "hostsim", "sim_gl.h")] + [os.path.join(csrc, f) for f in ("poseidon.h", "poseidon_tables.h", "gl.h", "ntt16.h", "ntt.h", "ext3.h")]
     if os.path.exists(SO) and all(os.path.getmtime(d) <= os.path.getmtime(SO) for d in deps):
         return SO
     tmp = "%s.%d.tmp" % (SO, os.getpid())

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import air_programs as A
+import arith_cases as AC
 import oracle_lib as O
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim"))
@@ -139,7 +140,7 @@ def test_lookup_air_one_definition_three_ways():
 def test_cubic_and_prefix_sum_primitives(hs):
     rng = np.random.default_rng(2)
     u64p = ctypes.POINTER(ctypes.c_uint64)
-    for m in (A.CUBIC_MODULUS, (1, 1), (5, 0), (int(rng.integers(1, P, dtype=np.uint64)), int(rng.integers(0, P, dtype=np.uint64)))):
+    for m in AC.cubic_moduli(rng):
         for _ in range(20):
             a = tuple(int(v) for v in rng.integers(0, P, 3, dtype=np.uint64))
             b = tuple(int(v) for v in rng.integers(0, P, 3, dtype=np.uint64))

@@ -241,6 +241,41 @@ def test_fri_prove_matches_oracle_on_random_instances(prover, seed):
     F.verify_both(spec, got)
 
 
+# every buffer state a challenger can hand to prove_openings: n_input 0 .. 7 with an empty output buffer, and an empty input buffer
+# with 1 .. 8 squeezed elements left
+INCOMING = [("input", k) for k in range(8)] + [("output", k) for k in range(1, 9)]
+
+
+def bring_to(kind, k):
+    def traffic(be, c):
+        be.challenges(c, 1)                                  # whatever was buffered is absorbed: n_input = 0
+        be.observe(c, np.arange(1, 9, dtype=np.uint64))      # eight elements: one permutation, n_input = 0, n_output = 8
+        if kind == "input":
+            be.challenges(c, 8)                              # n_output = 0
+            if k:
+                be.observe(c, np.arange(100, 100 + k, dtype=np.uint64))
+        elif k < 8:
+            be.challenges(c, 8 - k)
+    return traffic
+
+
+@pytest.mark.parametrize("device_transcript", [0, 1])
+@pytest.mark.parametrize("kind,k", INCOMING, ids=["%s%d" % s for s in INCOMING])
+def test_fri_prove_from_every_incoming_buffer_state(prover, kind, k, device_transcript):
+    """transcript.h `k_step` takes the buffer counters from the challenger it is handed: a degree-4 instance proved from every state
+    of the incoming challenger's two buffers, bytes and outgoing state against the oracle, under both transcript modes"""
+    spec = F.random_instance(11, degree_bits=4)
+    want = F.run_instance(F.OracleBackend(), spec, before_prove=bring_to(kind, k))
+    prover.set_device_transcript(device_transcript)
+    try:
+        got = F.run_instance(F.GpuBackend(prover), spec, before_prove=bring_to(kind, k))
+    finally:
+        prover.set_device_transcript(-1)
+    assert got["state_before"] == want["state_before"]
+    assert got["proof"] == want["proof"], (kind, k)
+    assert got["state_after"] == want["state_after"]
+
+
 def test_fri_prove_with_injected_pow_witness(prover):
     spec = F.random_instance(3)
     spec["pow_bits"] = 5

@@ -129,7 +129,34 @@ def test_toy_air_batch_equals_the_oracle_instance_by_instance(prover, db, B, dev
             g.close()
 
 
-# ---- 2. per-instance uniforms on the seeded small random shapes ----------------------------------------------------------
+LOCKSTEP_PREFIXES = (0, 1, 3, 7, 8, 9, 13)
+
+
+@pytest.mark.parametrize("device_transcript", [0, 1])
+def test_prefixes_of_every_buffer_state_in_one_batch(prover, device_transcript):
+    """transcript.h `k_step` reads the buffer counters of a wave's first challenger for all five. Seven instances (two waves, the
+    second partial) whose incoming challengers have absorbed 0, 1, 3, 7, 8, 9 and 13 elements — every one in another buffer
+    state: empty, partly filled, one short of a permutation, just permuted, permuted and filling again — must still prove what the
+    oracle proves one at a time, and hand back its challenger."""
+    db, B = 4, len(LOCKSTEP_PREFIXES)
+    c, ma, mb = A.lookup_programs()
+    op = [x.oracle() for x in (c, ma, mb)]
+    od, okeep = O.stark_desc(db, 1, 2, O.fri_params(db, 1, 2, 5, 12, (2,)), A.LOOKUP_K0, op[0], A.LOOKUP_K1, 3, steps=A.lookup_steps(op[1], op[2]))
+    rng = np.random.default_rng(41)
+    traces = [A.lookup_trace(1 << db, cheat=CHEATS[i % 3]) for i in range(B)]
+    prefixes = [rng.integers(0, P, n, dtype=np.uint64) for n in LOCKSTEP_PREFIXES]
+    pows = [None] * B
+    gd, keep, gp = toy_desc(prover, db)
+    prover.set_device_transcript(device_transcript)
+    try:
+        batch_matches(prover, gd, od, traces, prefixes, pows)
+    finally:
+        prover.set_device_transcript(-1)
+        for g in gp:
+            g.close()
+
+
+# ---- 2. per-instance uniforms on the seeded small random shapes----------------------------------------------------------
 def random_shape(seed):
     """the shape generator of test_gpu_air.py::test_stark_prove_bytes_on_small_random_shapes (same seeds, same draws), as builders"""
     rng = np.random.default_rng(9000 + seed)

@@ -3,10 +3,12 @@ and checked against the oracle: lazy reductions, limb-plane MDS, full permutatio
 import ctypes
 import os
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import arith_cases as AC
 import oracle_lib as O
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim"))
@@ -71,18 +73,15 @@ def test_permutation_matches_oracle(hs):
 def test_mul_pow2_shifts(hs):
     hs.hs_mul_pow2.restype = ctypes.c_uint64
     hs.hs_mul_pow2.argtypes = [ctypes.c_uint64, ctypes.c_int]
-    rng = np.random.default_rng(2)
-    vals = [int(x) % P for x in rng.integers(0, 2**64, 200, dtype=np.uint64)] + [0, 1, P - 1, P - 2, 0xFFFFFFFF,
-                                                                                 0xFFFFFFFF00000000, 1 << 63]
-    for k in (0, 1, 5, 12, 24, 31, 32, 33, 36, 48, 60, 63, 64, 65, 72, 84, 95):
+    vals = AC.mul_pow2_operands()
+    for k in AC.MUL_POW2_SHIFTS:
         for x in vals:
             assert hs.hs_mul_pow2(x, k) == (x << k) % P, (x, k)
 
 
 def test_radix16_register_butterfly_is_a_16_point_dif_ntt(hs):
     hs.hs_round16.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
-    x = O.splitmix64_felts(5, 16)
-    x[0], x[1], x[2] = P - 1, 0, 1
+    x = AC.round16_inputs()
     got = x.copy()
     hs.hs_round16(got.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), 0)
     assert (got == O.bit_reverse(O.ntt(x))).all()
@@ -143,16 +142,15 @@ def test_double_precision_layer_identities(hs):
     planes against the integer planes on lazy u64 states."""
     pd = ctypes.POINTER(ctypes.c_double)
     hs.hs_dom_d.argtypes = [ctypes.c_int, pd, pd]
-    C = [17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20]
-    rng = np.random.default_rng(4)
+    C = AC.MDS_C
+    rng, vectors = AC.dom_vectors()
 
     def dom(op, v):
         a = (ctypes.c_double * 12)(*[float(x) for x in v])
         b = (ctypes.c_double * 12)()
         hs.hs_dom_d(op, a, b)
         return [x for x in b]
-    for _ in range(200):
-        s = [int(x) for x in rng.integers(-(1 << 40), 1 << 40, 12)]
+    for s in vectors:
         u = dom(0, s)
         o = dom(1, u)
         y = dom(3, o)
@@ -163,13 +161,11 @@ def test_double_precision_layer_identities(hs):
         assert dom(2, w) == o
     p64 = ctypes.POINTER(ctypes.c_uint64)
     hs.hs_mds_layer.argtypes = [p64, ctypes.c_int]
-    M = (1 << 64) - 1
-    states = [[0] * 12, [M] * 12, [P - 1] * 12, [M, 0] * 6] + [[int(x) for x in rng.integers(0, 1 << 64, 12, dtype=np.uint64)] for _ in range(300)]
-    for st in states:
+    for st in AC.lazy_states(rng):
         a, b = (ctypes.c_uint64 * 12)(*st), (ctypes.c_uint64 * 12)(*st)
         hs.hs_mds_layer(a, 0)
         hs.hs_mds_layer(b, 1)
-        want = [(sum(C[i] * st[(i + r) % 12] for i in range(12)) + (8 * st[0] if r == 0 else 0)) % P for r in range(12)]
+        want = AC.mds_py(st)
         assert list(a) == want and list(b) == want
 
 
@@ -202,10 +198,9 @@ def test_double_precision_magnitudes(hs):
         assert x < 1 << 53
     assert 4 * x + 8 * n < (1 << 51) - (1 << 32)   # leaving: natural limbs (T^-1' adds four products) + diagonal
     # the conversion itself at its limits, against exact integers
-    for l, h, c in ((0, 0, 0), ((1 << 51) - (1 << 32) - 1, (1 << 51) - (1 << 32) - 1, P - 1), (-(1 << 51) + 1, -(1 << 51) + 1, 5), (-1, 0, 0), (0, -1, 0),
-                    (123456789012345, -98765432109876, 0xFFFFFFFF00000000)):
+    for l, h, c in AC.RECOMBINE_CONST_CASES:
         got = hs.hs_recombine_d(float(l), float(h), c)
-        assert got % P == (l + (h << 32) + c + ((0x433 << 52) + (1 << 51)) * (1 + (1 << 32))) % P, (l, h, c)   # c is stored minus that offset
+        assert got % P == (l + (h << 32) + c + AC.RECOMBINE_OFFSET) % P, (l, h, c)   # c is stored minus that offset
 
 
 # ---- BLS12-381 device formulas (csrc/bls12_381.h) on the host ------------------------------------------------
@@ -219,8 +214,7 @@ def _from_w32(w):
 
 def test_bls_field_ops_match_python_integers(hs):
     p, r, G = O.bls_constants()
-    rng = np.random.default_rng(4)
-    vals = [0, 1, 2, p - 1, p - 2, (1 << 380) + 12345, G[0], G[1]] + [int.from_bytes(rng.bytes(48), "little") % p for _ in range(40)]
+    vals = AC.bls_fp_values()
     out = (ctypes.c_uint32 * 12)()
     for i in range(len(vals) - 1):
         a, b = vals[i], vals[i + 1]
@@ -249,7 +243,6 @@ def test_bls_loose_field_primitives(hs):
     product), for operands anywhere below 32 p — and for the product also with limbs up to 2^29."""
     p, r, G = O.bls_constants()
     R = 1 << 392
-    rng = np.random.default_rng(14)
     out = (ctypes.c_uint32 * 14)()
     M28 = (1 << 28) - 1
 
@@ -257,8 +250,7 @@ def test_bls_loose_field_primitives(hs):
         hs.hs_bls_lz_op(op, _limbs28(a) if isinstance(a, int) else a, _limbs28(b) if isinstance(b, int) else b, out)
         assert all(x <= M28 for x in out), "limbs not normalised"
         return _from_limbs28(out)
-    vals = [0, 1, p - 1, p, p + 1, 2 * p - 1, 8 * p, 16 * p - 1, 16 * p, 22 * p - 1, 31 * p, 32 * p - 1]
-    vals += [int.from_bytes(rng.bytes(49), "little") % (32 * p) for _ in range(40)]
+    vals, rng = AC.bls_loose_values()
     Rinv = pow(R, -1, p)
     for a in vals:
         for b in vals[::3]:
@@ -295,8 +287,6 @@ def test_bls_loose_bucket_accumulation(hs):
     branch (the same point twice in a row, and a point equal to the running sum), and cancellation to infinity and on."""
     p, r, G = O.bls_constants()
     G2 = O.bls_g2_generator()
-    rng = np.random.default_rng(15)
-
     def flat1(P):
         return list(_w32(P[0])) + list(_w32(P[1]))
 
@@ -320,7 +310,7 @@ def test_bls_loose_bucket_accumulation(hs):
         for P in pts:
             acc = P if acc is None else add(acc, P)
         return acc
-    ks = [int.from_bytes(rng.bytes(32), "little") % r for _ in range(40)]
+    ks = AC.bls_bucket_scalars()
     g1 = [O.bls_g1_mul(G, k) for k in ks]
     assert chain1(g1) == total(O.bls_g1_add, g1)
     assert chain1(g1[:1]) == g1[0]
@@ -342,8 +332,6 @@ def test_bls_loose_bucket_accumulation(hs):
 
 def test_bls_group_law_matches_oracle(hs):
     p, r, G = O.bls_constants()
-    rng = np.random.default_rng(5)
-
     def run(op, P, Q, k=0):
         pxy = (ctypes.c_uint32 * 24)(*(list(_w32(P[0])) + list(_w32(P[1])))) if P else (ctypes.c_uint32 * 24)()
         qxy = (ctypes.c_uint32 * 24)(*(list(_w32(Q[0])) + list(_w32(Q[1])))) if Q else (ctypes.c_uint32 * 24)()
@@ -351,7 +339,7 @@ def test_bls_group_law_matches_oracle(hs):
         inf = hs.hs_bls_g1_op(op, pxy, 0 if P else 1, qxy, 0 if Q else 1, k, out)
         return None if inf else (_from_w32(out[:12]), _from_w32(out[12:]))
 
-    pts = [O.bls_g1_mul(G, int.from_bytes(rng.bytes(32), "little") % r) for _ in range(5)] + [G]
+    pts = AC.bls_g1_points()
     neg = lambda P: (P[0], p - P[1])
     for A in pts:
         for B in pts[:3]:
@@ -360,7 +348,7 @@ def test_bls_group_law_matches_oracle(hs):
         assert run(0, A, A) == run(1, A, A) == run(2, A, None) == O.bls_g1_mul(A, 2)     # the doubling branch
         assert run(0, A, neg(A)) is None and run(1, A, neg(A)) is None                    # the cancelling branch
         assert run(0, A, None) == A and run(0, None, A) == A and run(1, None, A) == A
-        for k in (0, 1, 2, 3, 255, 65535, 40000):
+        for k in AC.GROUP_SMALL_K:
             assert run(3, A, None, k) == O.bls_g1_mul(A, k)
     assert run(2, None, None) is None and run(3, None, None, 7) is None
 
@@ -369,15 +357,13 @@ def test_bls_fp2_and_g2_formulas(hs):
     """The G2 instantiation of the templated group law (coordinates in F_p^2) against the oracle, on the host."""
     p, r, _ = O.bls_constants()
     G2 = O.bls_g2_generator()
-    rng = np.random.default_rng(6)
+    pairs, rng = AC.bls_fp2_pairs()
 
     def w2(c):   # (c0, c1) -> 24 words
         return (ctypes.c_uint32 * 24)(*(list(_w32(c[0])) + list(_w32(c[1]))))
 
     out = (ctypes.c_uint32 * 24)()
-    for _ in range(20):
-        a = (int.from_bytes(rng.bytes(48), "little") % p, int.from_bytes(rng.bytes(48), "little") % p)
-        b = (int.from_bytes(rng.bytes(48), "little") % p, int.from_bytes(rng.bytes(48), "little") % p)
+    for a, b in pairs:
         hs.hs_bls_fp2_op(0, w2(a), w2(b), out)
         assert (_from_w32(out[:12]), _from_w32(out[12:])) == ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)
         hs.hs_bls_fp2_op(1, w2(a), w2(a), out)
@@ -397,7 +383,7 @@ def test_bls_fp2_and_g2_formulas(hs):
         inf = hs.hs_bls_g2_op(op, pt_words(P), 0 if P else 1, pt_words(Q), 0 if Q else 1, k, o)
         return None if inf else ((_from_w32(o[0:12]), _from_w32(o[12:24])), (_from_w32(o[24:36]), _from_w32(o[36:48])))
 
-    pts = [O.bls_g2_mul(G2, int.from_bytes(rng.bytes(32), "little") % r) for _ in range(3)] + [G2]
+    pts = AC.bls_g2_points(rng)
     neg = lambda P: (P[0], ((-P[1][0]) % p, (-P[1][1]) % p))
     for A in pts:
         for B in pts[:2]:
@@ -411,8 +397,7 @@ def test_bls_fp2_and_g2_formulas(hs):
 
 def test_bls_scalar_field_ops(hs):
     _, r, _ = O.bls_constants()
-    rng = np.random.default_rng(12)
-    vals = [0, 1, 2, r - 1, r - 2, (1 << 254) + 99, 7] + [int.from_bytes(rng.bytes(32), "little") % r for _ in range(40)]
+    vals, rng = AC.bls_fr_values()
     out = (ctypes.c_uint32 * 8)()
     for i in range(len(vals) - 1):
         a, b = vals[i], vals[i + 1]
@@ -601,3 +586,22 @@ def test_device_memory_owners(hs):
             ops.append((op, a, b, c_))
         res, c = _mem_script(hs, 16 * MB, 24 * MB, ops)
         assert all(r >= 0 or r == -2 for r in res)   # -2: the allocator's out-of-memory, never a disagreement of pointer and size
+
+
+def test_double_precision_worst_case_vectors(hs):
+    """The magnitudes that test_double_precision_magnitudes bounds by interval arithmetic, executed: for every output component of
+    dom_mul_d<true>, dom_mul2_d and dom_next_z the input with every entry at the bound of a normalised limb (2^31 + 2^20 in units
+    of 1, and the same in units of 2^32) and the signs that make the component the sum of the absolute values, and its negation. The
+    exact rational result is a double, and the code returns it: nothing rounds at the largest values a layer can produce."""
+    pd = ctypes.POINTER(ctypes.c_double)
+    hs.hs_dom_d.argtypes = [ctypes.c_int, pd, pd]
+    cases = AC.worst_case_vectors()
+    assert len(cases) == 25 * 4
+    for op, s, comp, want in cases:
+        exact = AC.dom_exact(op, s)
+        assert exact[comp] == want and all(AC.representable(v) for v in exact), (op, comp)
+        assert all(AC.representable(v) for v in s)
+        a = (ctypes.c_double * 13)(*[float(v) for v in s])
+        b = (ctypes.c_double * 12)()
+        hs.hs_dom_d(op, a, b)
+        assert [Fraction(v) for v in b] == exact, (op, comp, [float(v) for v in s])

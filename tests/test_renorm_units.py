@@ -23,9 +23,7 @@ pd = ctypes.POINTER(ctypes.c_double)
 PERMUTE, ABSORB, SQUEEZE, NODE, TEXTBOOK = range(5)
 # form -> (live words, canonical on exit)
 LIVE = {PERMUTE: (slice(0, 12), True), ABSORB: (slice(8, 12), False), SQUEEZE: (slice(0, 4), True), NODE: (slice(0, 4), True)}
-U = Fraction(1, 1 << 32)            # one old unit in the new ones
-LIM = (1 << 31) + (1 << 20)         # a normalised limb, old units (the magnitude comment above dom_mul_d)
-BOUND = 1 << 50                     # above every limb entering the normalisation (2^49.3, old units), two fractional bits included
+from arith_cases import BOUND, LIM, U, absorb_chunks, exact_renorm32, input_states, recombine_limbs, renorm_cases, representable, rne  # noqa: E402,F401
 
 
 @pytest.fixture(scope="module")
@@ -41,21 +39,6 @@ def hs():
 
 
 # ---- the permutation forms ------------------------------------------------------------------------------------------
-def input_states():
-    """random canonical states, all zero, all p - 1, rows of boundary words, lazy words at 2^64 - 1 (capacity only, everywhere)"""
-    rng = np.random.default_rng(31)
-    st = O.splitmix64_felts(0x2E4032, 12 * 160).reshape(-1, 12).copy()
-    st[0] = 0
-    st[1] = P - 1
-    st[2] = M64
-    st[3, 8:] = M64
-    edge = np.array([0, 1, P - 1, P - 2, 0xFFFFFFFF, 0x100000000, 0xFFFFFFFF00000000, 0xFFFFFFFE00000001, 1 << 63, M64, M64 - 0xFFFFFFFF, P, P + 1],
-                    np.uint64)
-    for i in range(4, 64):
-        st[i] = rng.choice(edge, 12)
-    return st
-
-
 def run(hs, st, form):
     out = st.copy()
     assert hs.hs_rn_permute(out.ctypes.data_as(p64), out.shape[0], form) == 0
@@ -83,10 +66,7 @@ def test_permutation_forms_equal_textbook_and_oracle(hs, form):
 def test_17_chained_absorbs(hs):
     """the middle of a 135-column leaf: 17 capacity-only permutations, the lazy capacity carried from one to the next"""
     n = 24
-    chunks = O.splitmix64_felts(0xAB50, 17 * n * 8).reshape(17, n, 8).copy()
-    chunks[2] = P - 1
-    chunks[5] = 0
-    chunks[9] = M64
+    chunks = absorb_chunks(n)
     a = np.zeros((n, 12), np.uint64)
     b = a.copy()
     for c in range(17):
@@ -103,63 +83,6 @@ def test_17_chained_absorbs(hs):
 
 
 # ---- the normalisation alone, against exact rationals ------------------------------------------------------------------
-def rne(x):
-    """round to nearest, ties to even (what rint does in the default rounding mode)"""
-    f = x.numerator // x.denominator
-    r = x - f
-    if r > Fraction(1, 2) or (r == Fraction(1, 2) and f % 2):
-        f += 1
-    return f
-
-
-def representable(x):
-    return Fraction(float(x)) == x
-
-
-def exact_renorm32(L, H):
-    """renorm32_d step by step in exact arithmetic; every intermediate must be a double (then no operation rounds: an IEEE
-    operation whose exact result is representable returns it)"""
-    c = rne(L)
-    l1 = L - c
-    h1 = H + c * U
-    t = rne(h1)
-    h2 = h1 - t * (1 - U)
-    l2 = l1 - t * U
-    steps = (Fraction(c), l1, h1, Fraction(t), h2, l2)
-    assert all(representable(s) for s in steps), (L, H, steps)
-    return l2, h2, c, t
-
-
-def renorm_cases():
-    """(l, h) in OLD units (value l + 2^32 h), Fractions with denominators up to 4"""
-    rng = np.random.default_rng(8)
-    B, T31, T32 = BOUND, 1 << 31, 1 << 32
-    cases = []
-    q = lambda a, b=0: Fraction(4 * a + b, 4)
-    # the bounds of the magnitude comment: just inside 2^50, two fractional bits
-    for l in (q(B - 1, 3), q(-B + 1, -3), q(0), q(1), q(-1), q(0, 1), q(0, -1)):
-        for h in (q(B - 1, 3), q(-B + 1, -3), q(0), q(1), q(-1)):
-            cases.append((l, h))
-    # quarter-integer limbs
-    for _ in range(1500):
-        l, h = (int(v) for v in rng.integers(-B + 1, B - 1, 2))
-        cases.append((q(l, int(rng.integers(0, 4))), q(h, int(rng.integers(0, 4)))))
-    # every tie: l an odd multiple of 2^31 (c decides between two even / odd neighbours), h likewise once c / 2^32 has gone in
-    for k in list(range(-9, 10, 2)) + [(1 << 18) - 1, -(1 << 18) + 1, (1 << 19) - 3, 54321]:
-        cases.append((Fraction(k * T31), Fraction(0)))
-        cases.append((Fraction(0), Fraction(k * T31)))
-        cases.append((Fraction(k * T31), Fraction((k + 2) * T31)))
-        c = rne(Fraction(k, 2))
-        cases.append((Fraction(k * T31), Fraction(3 * T31 - c)))   # h + c lands exactly on a tie of the second rounding
-    # carries: c != 0 and t != 0 with all four sign combinations, small and large
-    for cs in (1, -1):
-        for ts in (1, -1):
-            for cm, tm in ((1, 1), (3, 2), (1 << 17, 1 << 17), ((1 << 18) - 1, (1 << 18) - 1)):
-                cases.append((Fraction(cs * cm * T32 + cs * 5), Fraction(ts * tm * T32 + ts * 7)))
-                cases.append((q(cs * cm * T32, cs * 1), q(ts * tm * T32 + ts * (T31 - 1), ts * 3)))
-    return cases
-
-
 def test_renorm32_against_exact_rationals(hs):
     cases = renorm_cases()
     seen = set()
@@ -204,9 +127,7 @@ def test_scaled_constants_reproduce_the_unscaled_integers(hs):
     import gen_tables
     dk, dlast = gen_tables.plane_constants(gen_tables.round_constants(), first_too=True)
     B32 = (0x413 << 52) + (1 << 51)
-    rng = np.random.default_rng(12)
-    lim = (1 << 51) - (1 << 32) - 1       # recombine_d's range
-    limbs = [(0, 0), (lim, lim), (-lim, -lim), (lim, -lim), (-1, 0), (0, -1), (1, 1)] + [tuple(int(v) for v in rng.integers(-lim, lim, 2)) for _ in range(40)]
+    limbs = recombine_limbs()
     for name, want, t_old, t_new in (("POSEIDON_DOMD32_K", dk, 0, 2), ("POSEIDON_DOMD32_LAST", dlast, 1, 3)):
         got = parse_table(name)
         assert len(got) == 2 * len(want)
