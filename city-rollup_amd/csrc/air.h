@@ -145,6 +145,31 @@ inline std::string analyse(Program &p) {
   return "";
 }
 
+// Does an analysed map program load a column it also stores, when input column c lies at byte address in + c * n * 8 and output
+// column j at out + j * n * 8 (by index instead of by address: in = 0, out = the first output column's index * n * 8)? The rule is
+// syntactic: every LOCAL / NEXT and every STORE of the ops as given counts, live or dead. The stores of a map run as concurrent
+// segments and a NEXT load crosses lanes, so such a program has no defined result. true: *in_col / *out_col are the first pair
+// in store order.
+inline bool map_self_read(const Program &p, uint64_t in, uint64_t out, uint64_t n, uint32_t *in_col, uint32_t *out_col) {
+  if (!n) return false;
+  std::vector<uint8_t> loaded(p.n_columns, 0);
+  for (const RawOp &o : p.ops)
+    if (is_load(o.op)) loaded[o.a] = 1;
+  const uint64_t w = n * 8;
+  for (const RawOp &o : p.ops) {
+    if (o.op != R_STORE) continue;
+    const uint64_t lo = out + o.a * w, hi = lo + w;  // the stored bytes [lo, hi)
+    if (hi <= in) continue;
+    for (uint64_t c = lo > in ? (lo - in) / w : 0; c < p.n_columns && in + c * w < hi; c++)
+      if (loaded[c]) {
+        *in_col = (uint32_t)c;
+        *out_col = o.a;
+        return true;
+      }
+  }
+  return false;
+}
+
 struct Compiled {
   std::vector<uint64_t> code;
   std::vector<uint32_t> seg_off;      // [S + 1] into code

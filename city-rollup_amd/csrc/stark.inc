@@ -284,6 +284,15 @@ void air_eval_ext_row(const air::Program &P, const gl::Ext *local, const gl::Ext
   }
 }
 
+// A map program must not load a column it also stores (air.h map_self_read: the stores run as concurrent segments). in / out: byte
+// addresses of the first input / output column, or indices scaled by n * 8; step < 0: a call of cp_air_map_dev, not a STARK step.
+int map_self_read_refused(cp_ctx *ctx, const air::Program &P, uint64_t in, uint64_t out, size_t n, long step) {
+  uint32_t in_col = 0, out_col = 0;
+  if (!air::map_self_read(P, in, out, n, &in_col, &out_col)) return CP_OK;
+  if (step < 0) return set_error(ctx, CP_ERR_INVALID_ARG, "the map program loads extended column %u, which it also stores", out_col);
+  return set_error(ctx, CP_ERR_INVALID_ARG, "step %zu: the map program loads extended column %u, which it also stores", (size_t)step, out_col);
+}
+
 struct StarkShape {
   int db, rb, ch, q;
   size_t n, k0, k1, kt, kq;
@@ -318,6 +327,7 @@ int stark_shape(cp_ctx *ctx, const cp_stark_desc *d, bool prover, StarkShape &s)
         if (m->P.n_columns != s.kt || m->P.n_out_columns != s.k1 || m->P.n_public != d->n_public || m->P.n_global != d->n_global ||
             m->P.n_challenge != d->n_round_challenges)
           return set_error(ctx, CP_ERR_INVALID_ARG, "step %zu: the map program's columns / outputs / publics / globals / challenges differ from the description", i);
+        CP_TRY(map_self_read_refused(ctx, m->P, 0, (uint64_t)s.k0 * s.n * 8, s.n, (long)i));  // extended column e is input column k0 + e
       } else if (st.kind == CP_STARK_STEP_CUBIC_INVERSE) {
         if (st.first > s.k1 || (uint64_t)st.count * 3 > s.k1 - st.first) return set_error(ctx, CP_ERR_INVALID_ARG, "step %zu: columns out of range", i);
         if (st.modulus[0] >= gl::P || st.modulus[1] >= gl::P) return set_error(ctx, CP_ERR_INVALID_ARG, "step %zu: modulus is not canonical", i);
@@ -654,6 +664,7 @@ int cp_air_map_dev(cp_ctx *ctx, const cp_air_program *program, const uint64_t *i
   if (prog->device != ctx->device) return set_error(ctx, CP_ERR_INVALID_ARG, "the program belongs to another device");
   if (n == 0) return CP_OK;
   if ((P.n_columns && !in_cols_dev) || (P.n_out_columns && !out_cols_dev)) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL column arrays");
+  CP_TRY(map_self_read_refused(ctx, P, (uint64_t)(uintptr_t)in_cols_dev, (uint64_t)(uintptr_t)out_cols_dev, n, -1));
   std::vector<uint64_t> uni;
   CP_TRY(air_uniform_table(ctx, P, publics, globals, challenges, uni));
   ArenaScope arena_scope(ctx, ctx->arena.used == 0);

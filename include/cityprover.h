@@ -633,7 +633,10 @@ int cp_air_quotient_commit(cp_ctx *ctx, const cp_air_program *program, cp_poly_b
                            int quotient_degree_bits, const uint64_t *publics, const uint64_t *globals,
                            const uint64_t *challenges, const uint64_t *alphas, size_t n_alphas, cp_poly_batch **quotient_out);
 /* A map program over n rows. in_cols_dev: n_columns x n values (column-major, natural row order; the next row of the last
- * row is row 0); out_cols_dev: n_out_columns x n, only the stored columns are written. publics / globals / challenges: host. */
+ * row is row 0); out_cols_dev: n_out_columns x n, only the stored columns are written. publics / globals / challenges: host.
+ * An input column that the program loads (LOCAL or NEXT, whether or not the value is used) and an output column that it stores
+ * must not overlap: the stores run concurrently, so such a program has no defined result, and the call is refused
+ * (CP_ERR_INVALID_ARG). Columns that are only loaded, or only stored, may share an array. */
 int cp_air_map_dev(cp_ctx *ctx, const cp_air_program *program, const uint64_t *in_cols_dev, uint64_t *out_cols_dev, size_t n,
                    const uint64_t *publics, const uint64_t *globals, const uint64_t *challenges);
 /* count x n cubic-extension elements, element e of row i = (cols[3e][i], cols[3e+1][i], cols[3e+2][i]) with columns n apart,
@@ -650,7 +653,9 @@ enum { CP_STARK_STEP_MAP = 0, CP_STARK_STEP_CUBIC_INVERSE = 1, CP_STARK_STEP_PRE
 typedef struct cp_stark_step {
   int kind;
   /* MAP: `program` (n_columns = n_trace_columns + n_extended_columns: a row is the execution trace followed by the extended
-   *   columns as filled so far; n_out_columns = n_extended_columns; n_challenge = n_round_challenges)
+   *   columns as filled so far by EARLIER steps; n_out_columns = n_extended_columns; n_challenge = n_round_challenges). A program
+   *   must not load a column it stores - an op LOCAL / NEXT of column n_trace_columns + e and a STORE of column e in one program,
+   *   used or not: the prover refuses such a description (CP_ERR_INVALID_ARG) before it stages anything
    * CUBIC_INVERSE: extended columns [first, first + 3 * count) as `count` cubic elements, inverted, modulus as above
    * PREFIX_SUM: extended columns [first, first + count), flags bit 0 = exclusive */
   const cp_air_program *program;

@@ -273,4 +273,16 @@ int hs_air_point(int kind, const uint32_t *ops, size_t n_ops, const uint64_t *co
   info_out[0] = C.n_segments(); info_out[1] = C.n_slots; info_out[2] = (uint32_t)C.code.size(); info_out[3] = (uint32_t)P.n_live; info_out[4] = P.max_degree;
   return 0;
 }
+// air::map_self_read of a map program (dims as above) whose input columns start at byte address `in` and output columns at `out`, n rows:
+// 1 and the first pair (cols_out[0] = the loaded input column, cols_out[1] = the stored output column), 0 = none, -1 = malformed program
+int hs_air_map_self_read(const uint32_t *ops, size_t n_ops, const uint32_t *dims, uint64_t in, uint64_t out, uint64_t n, uint32_t *cols_out, char *err) {
+  air::Program P;
+  P.kind = 1;
+  P.ops.resize(n_ops);
+  if (n_ops) memcpy(P.ops.data(), ops, n_ops * 16);
+  P.n_columns = dims[0]; P.n_public = dims[1]; P.n_global = dims[2]; P.n_challenge = dims[3]; P.n_out_columns = dims[4];
+  const std::string why = air::analyse(P);
+  if (!why.empty()) { snprintf(err, 256, "%s", why.c_str()); return -1; }
+  return air::map_self_read(P, in, out, n, &cols_out[0], &cols_out[1]) ? 1 : 0;
+}
 }

@@ -254,6 +254,46 @@ def test_analyser_refuses_malformed_programs(hs):
     bad(lambda b: (b.consts.append(P), b.ops.append((A.CONST, 0, 0, 0))), "canonical")
 
 
+def test_a_map_program_that_loads_what_it_stores_is_found(hs):
+    """air.h map_self_read, the rule behind the refusal of cp_stark_prove / cp_stark_prove_batch / cp_air_map_dev: a LOCAL / NEXT
+    load of an input column and a STORE of an output column that overlap it, live or dead, by index (in = 0, out = k0 n 8: extended
+    column e is input column k0 + e) and by address"""
+    k0, k1, n = 3, 4, 16
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    hs.hs_air_map_self_read.argtypes = [u32p, ctypes.c_size_t, u32p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, u32p, ctypes.c_char_p]
+
+    def hit(build, in_=0, out=k0 * n * 8, rows=n):
+        b = A.Builder(A.MAP, k0 + k1, n_out_columns=k1)
+        build(b)
+        assert not b.consts
+        ops, _ = b.arrays()
+        dims = np.array([b.n_columns, 0, 0, 0, b.n_out_columns], dtype=np.uint32)
+        cols, err = np.zeros(2, np.uint32), ctypes.create_string_buffer(256)
+        rc = hs.hs_air_map_self_read(ops.ctypes.data_as(u32p), len(ops), dims.ctypes.data_as(u32p), in_, out, rows, cols.ctypes.data_as(u32p), err)
+        assert rc in (0, 1), err.value
+        return (int(cols[0]), int(cols[1])) if rc else None
+    assert hit(lambda b: b.store(1, b.add(b.local(0), b.next(2)))) is None                   # trace columns only
+    assert hit(lambda b: b.store(1, b.local(k0 + 0))) is None                                # an extended column an EARLIER step stored
+    assert hit(lambda b: (b.store(0, b.local(1)), b.store(3, b.next(k0 + 2)))) is None
+    assert hit(lambda b: b.store(1, b.local(k0 + 1))) == (k0 + 1, 1)                         # LOCAL self-read
+    assert hit(lambda b: b.store(2, b.add(b.local(0), b.next(k0 + 2)))) == (k0 + 2, 2)       # NEXT self-read
+    assert hit(lambda b: (b.store(0, b.local(k0 + 3)), b.store(3, b.local(1)))) == (k0 + 3, 3)   # across two stores of one program
+    assert hit(lambda b: (b.local(k0 + 1), b.store(1, b.local(0)))) == (k0 + 1, 1)           # a dead load counts: the rule is syntactic
+    # by address: disjoint arrays, arrays that touch, a partial overlap of one column, outputs below the inputs
+    self_read = lambda b: b.store(1, b.local(k0 + 1))
+    base = 1 << 20
+    assert hit(self_read, base, base + (k0 + k1) * n * 8) is None
+    assert hit(self_read, base, base - k1 * n * 8) is None
+    assert hit(self_read, base, base + k0 * n * 8) == (k0 + 1, 1)
+    assert hit(self_read, base, base + k0 * n * 8 + 8) == (k0 + 1, 1)                        # output 1 = all but one element of input k0 + 1
+    assert hit(self_read, base, base + (k0 + 1) * n * 8 - 8) == (k0 + 1, 1)                  # output 1 begins at the last element of input k0 + 1
+    assert hit(self_read, base, base + (k0 + 1) * n * 8) is None                             # output 1 is input k0 + 2, which is not loaded
+    assert hit(self_read, base, base + (k0 + 1) * n * 8 + 8) is None                         # ... and one element of input k0 + 3
+    assert hit(self_read, base, base + (k0 - 1) * n * 8 + 8) == (k0 + 1, 1)                  # output 1 ends one element into input k0 + 1
+    assert hit(lambda b: b.store(0, b.local(0)), base, base - n * 8 + 8) == (0, 0)           # the output starts below the inputs
+    assert hit(self_read, base, base + k0 * n * 8, rows=0) is None                           # no rows: nothing is read or stored
+
+
 def test_constraint_degree(hs):
     def deg(build):
         b = A.Builder(A.CONSTRAINTS, 2)

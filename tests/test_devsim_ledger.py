@@ -14,6 +14,7 @@ EXCLUDED = {
     "hs_pool_script": "dev_pool.h over a counting allocator: host bookkeeping",
     "hs_mem_script": "dev_mem.h over a counting allocator: host bookkeeping",
     "hs_air_point": "air.h analyse + compile run on the host; the interpreter has its own GPU tests (tests/test_gpu_air.py)",
+    "hs_air_map_self_read": "air.h map_self_read: a host check of a map program's loads against its stores; the refusals have their own GPU tests (tests/test_gpu_air_semantics.py)",
     "hs_rn_units32": "reports a compile-time constant",
 }
 HOST_LOGIC = re.compile(r"^hs_(parallel_for|pool_|mem_|air_|rn_units32)")
