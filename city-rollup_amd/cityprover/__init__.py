@@ -126,10 +126,17 @@ class DeviceBuffer:
     def at(self, offset):
         return self.ptr + offset * 8
 
+    @classmethod
+    def view(cls, prover, ptr, n_elems):
+        """n_elems u64 at a device address that somebody else owns (a key's array): download / at work, free does nothing"""
+        self = cls.__new__(cls)
+        self.prover, self.n, self.ptr, self.borrowed = prover, int(n_elems), ptr, True
+        return self
+
     def free(self):
-        if self.ptr:
+        if self.ptr and not getattr(self, "borrowed", False):
             self.prover._check(self.prover.lib.cp_dev_free(self.prover.ctx, self.ptr))
-            self.ptr = None
+        self.ptr = None
 
 
 class Prover:
@@ -676,7 +683,26 @@ ABI["cp_msm_bls12381_g1"] = (ctypes.c_int, [_vp, _u64p, _u64p, _u8p, ctypes.c_si
 ABI["cp_msm_bls12381_g1_prepare_dev"] = (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp])
 ABI["cp_msm_bls12381_g1_dev"] = (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, _u64p, ctypes.POINTER(ctypes.c_int)])
 ABI["cp_msm_bls12381_g1_synthetic_points_dev"] = (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp])
+ABI["cp_fixed_base_mul_bls12381_g1_dev"] = (ctypes.c_int, [_vp, _u64p, _vp, ctypes.c_size_t, _vp, _vp])
 G1_AFFINE_BYTES = 112
+BLS_P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
+_BLS_RINV = pow(1 << 392, -1, BLS_P)   # the internal form is Montgomery, radix 2^392, in 14 limbs of 28 bits
+
+
+def _coords_to_host(buf, n, per_point, index=None):
+    """the coordinates of points in the library's internal form as canonical ints: (len(index), per_point)"""
+    limbs = buf.download(n * per_point * 7).view(np.uint32).reshape(n, per_point, 14)
+    rows = range(n) if index is None else index
+    return [[sum(int(l) << (28 * j) for j, l in enumerate(limbs[i, c])) * _BLS_RINV % BLS_P for c in range(per_point)] for i in rows]
+
+
+def _flags_buffer(prover, n):
+    return prover.alloc((n + 7) // 8)
+
+
+def flags_to_host(buf, n):
+    """a device byte-flag array of n entries (in a u64 buffer) as uint8"""
+    return buf.download((n + 7) // 8).view(np.uint8)[:n].copy()
 
 
 def _g1_out(xy, inf):
@@ -723,9 +749,38 @@ class G1Points:
         prover.sync()
         return self
 
-    def msm_dev(self, scalars_ptr):
+    @classmethod
+    def fixed_base(cls, prover, base, scalars_ptr, n):
+        """(points, flags): points[i] = scalars[i] * base for the n scalars (4 u64 each) at scalars_ptr, built on the device
+        (cp_fixed_base_mul_bls12381_g1_dev); flags: a device buffer of n bytes, 1 = the point at infinity. base: (x, y) ints."""
+        self = cls.__new__(cls)
+        self.prover, self.n = prover, n
+        self.buf = prover.alloc(max(n, 1) * G1_AFFINE_BYTES // 8)
+        flags = _flags_buffer(prover, max(n, 1))
+        g = np.array([(int(base[h]) >> (64 * i)) & (2**64 - 1) for h in range(2) for i in range(6)], dtype=np.uint64)
+        try:
+            prover._check(prover.lib.cp_fixed_base_mul_bls12381_g1_dev(prover.ctx, _ptr(g), scalars_ptr, n, self.buf.ptr, flags.ptr))
+            prover.sync()
+        except CityProverError:
+            self.buf.free()
+            flags.free()
+            raise
+        return self, flags
+
+    @classmethod
+    def view(cls, prover, ptr, n):
+        """n points of a set that somebody else owns (a key's)"""
+        self = cls.__new__(cls)
+        self.prover, self.n, self.buf = prover, n, DeviceBuffer.view(prover, ptr, n * G1_AFFINE_BYTES // 8)
+        return self
+
+    def to_host(self, index=None):
+        """the points (all, or those at `index`) as (x, y) ints: a test and debugging aid, Python arithmetic per point"""
+        return [tuple(c) for c in _coords_to_host(self.buf, self.n, 2, index)]
+
+    def msm_dev(self, scalars_ptr, inf_ptr=None):
         out, oi = np.zeros(12, np.uint64), ctypes.c_int()
-        self.prover._check(self.prover.lib.cp_msm_bls12381_g1_dev(self.prover.ctx, scalars_ptr, self.buf.ptr, None, self.n,
+        self.prover._check(self.prover.lib.cp_msm_bls12381_g1_dev(self.prover.ctx, scalars_ptr, self.buf.ptr, inf_ptr, self.n,
                                                                   _ptr(out), ctypes.byref(oi)))
         return _g1_out(out, oi)
 
@@ -738,6 +793,7 @@ ABI["cp_msm_bls12381_g2"] = (ctypes.c_int, [_vp, _u64p, _u64p, _u8p, ctypes.c_si
 ABI["cp_msm_bls12381_g2_prepare_dev"] = (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp])
 ABI["cp_msm_bls12381_g2_synthetic_points_dev"] = (ctypes.c_int, [_vp, _u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, _vp])
 ABI["cp_msm_bls12381_g2_dev"] = (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_size_t, _u64p, ctypes.POINTER(ctypes.c_int)])
+ABI["cp_fixed_base_mul_bls12381_g2_dev"] = (ctypes.c_int, [_vp, _u64p, _vp, ctypes.c_size_t, _vp, _vp])
 G2_AFFINE_BYTES = 224
 
 
@@ -785,9 +841,37 @@ class G2Points:
         prover.sync()
         return self
 
-    def msm_dev(self, scalars_ptr):
+    @classmethod
+    def fixed_base(cls, prover, base, scalars_ptr, n):
+        """G1Points.fixed_base over G2 (cp_fixed_base_mul_bls12381_g2_dev). base: ((x0, x1), (y0, y1)) ints."""
+        self = cls.__new__(cls)
+        self.prover, self.n = prover, n
+        self.buf = prover.alloc(max(n, 1) * G2_AFFINE_BYTES // 8)
+        flags = _flags_buffer(prover, max(n, 1))
+        (x0, x1), (y0, y1) = base
+        g = np.array([(int(c) >> (64 * i)) & (2**64 - 1) for c in (x0, x1, y0, y1) for i in range(6)], dtype=np.uint64)
+        try:
+            prover._check(prover.lib.cp_fixed_base_mul_bls12381_g2_dev(prover.ctx, _ptr(g), scalars_ptr, n, self.buf.ptr, flags.ptr))
+            prover.sync()
+        except CityProverError:
+            self.buf.free()
+            flags.free()
+            raise
+        return self, flags
+
+    @classmethod
+    def view(cls, prover, ptr, n):
+        self = cls.__new__(cls)
+        self.prover, self.n, self.buf = prover, n, DeviceBuffer.view(prover, ptr, n * G2_AFFINE_BYTES // 8)
+        return self
+
+    def to_host(self, index=None):
+        """the points (all, or those at `index`) as ((x0, x1), (y0, y1)) ints"""
+        return [((c[0], c[1]), (c[2], c[3])) for c in _coords_to_host(self.buf, self.n, 4, index)]
+
+    def msm_dev(self, scalars_ptr, inf_ptr=None):
         out, oi = np.zeros(24, np.uint64), ctypes.c_int()
-        self.prover._check(self.prover.lib.cp_msm_bls12381_g2_dev(self.prover.ctx, scalars_ptr, self.buf.ptr, None, self.n,
+        self.prover._check(self.prover.lib.cp_msm_bls12381_g2_dev(self.prover.ctx, scalars_ptr, self.buf.ptr, inf_ptr, self.n,
                                                                   _ptr(out), ctypes.byref(oi)))
         return _g2_out(out, oi)
 
@@ -955,6 +1039,76 @@ def groth16_prove_r1cs(prover, pk, r1cs, witness_ptr, r, s, out=None):
                                                             _ptr(oa), _ptr(ob), _ptr(oc)))
     val = lambda a: sum(int(v) << (64 * j) for j, v in enumerate(a))
     return ((val(oa[:6]), val(oa[6:])), ((val(ob[:6]), val(ob[6:12])), (val(ob[12:18]), val(ob[18:]))), (val(oc[:6]), val(oc[6:])))
+
+
+# ---- Groth16 setup: (constraint system, trapdoor) -> the proving key on the device and the verifying key ----
+class Groth16Trapdoor(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64 * 4) for name in ("tau", "alpha", "beta", "gamma", "delta")]
+
+
+class Groth16Vk(ctypes.Structure):
+    _fields_ = [("alpha_g1", ctypes.c_uint64 * 12), ("beta_g2", ctypes.c_uint64 * 24), ("gamma_g2", ctypes.c_uint64 * 24),
+                ("delta_g2", ctypes.c_uint64 * 24), ("n_public", ctypes.c_size_t)]
+
+
+ABI["cp_groth16_setup_bls12381"] = (_vp, [_vp, ctypes.POINTER(R1csDesc), ctypes.c_size_t, ctypes.POINTER(Groth16Trapdoor)])
+ABI["cp_groth16_key_destroy"] = (None, [_vp])
+ABI["cp_groth16_key_pk"] = (ctypes.c_int, [_vp, ctypes.POINTER(Groth16Pk)])
+ABI["cp_groth16_key_vk"] = (ctypes.c_int, [_vp, ctypes.POINTER(Groth16Vk), _u64p, _u8p])
+
+
+class Groth16Key:
+    """A proving key resident on the device, with its verifying key (cp_groth16_setup_bls12381)."""
+
+    def __init__(self, prover, handle):
+        self.prover, self.handle = prover, handle
+
+    @classmethod
+    def setup(cls, prover, n_constraints, n_wires, coeffs, matrices, n_public, tau, alpha, beta, gamma, delta, flags=0):
+        """The system as R1cs takes it; n_public counts wire 0; the five trapdoor scalars are ints (the caller's randomness)."""
+        desc, keep = r1cs_desc(n_constraints, n_wires, coeffs, matrices, flags)
+        td = Groth16Trapdoor()
+        for name, v in (("tau", tau), ("alpha", alpha), ("beta", beta), ("gamma", gamma), ("delta", delta)):
+            getattr(td, name)[:] = [(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)]
+        handle = prover.lib.cp_groth16_setup_bls12381(prover.ctx, ctypes.byref(desc), int(n_public), ctypes.byref(td))
+        del keep
+        if not handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+        return cls(prover, handle)
+
+    def pk(self):
+        """Groth16Pk: a view, valid until free()"""
+        pk = Groth16Pk()
+        self.prover._check(self.prover.lib.cp_groth16_key_pk(self.handle, ctypes.byref(pk)))
+        return pk
+
+    def vk(self):
+        """dict: alpha_g1, beta_g2, gamma_g2, delta_g2 as coordinate tuples of ints, n_public, ic: n_public points (None = infinity)"""
+        vk = Groth16Vk()
+        self.prover._check(self.prover.lib.cp_groth16_key_vk(self.handle, ctypes.byref(vk), None, None))
+        n = vk.n_public
+        xy, inf = np.zeros((n, 12), np.uint64), np.zeros(n, np.uint8)
+        self.prover._check(self.prover.lib.cp_groth16_key_vk(self.handle, ctypes.byref(vk), _ptr(xy), inf.ctypes.data_as(_u8p)))
+        val = lambda a: sum(int(v) << (64 * j) for j, v in enumerate(a))
+        g2 = lambda a: ((val(a[0:6]), val(a[6:12])), (val(a[12:18]), val(a[18:24])))
+        return {"alpha_g1": (val(vk.alpha_g1[0:6]), val(vk.alpha_g1[6:12])), "beta_g2": g2(vk.beta_g2), "gamma_g2": g2(vk.gamma_g2),
+                "delta_g2": g2(vk.delta_g2), "n_public": n,
+                "ic": [None if inf[i] else (val(xy[i, :6]), val(xy[i, 6:])) for i in range(n)]}
+
+    def point_sets(self):
+        """the five sets as G1Points / G2Points views and the two flag arrays as uint8 (tests, inspection)"""
+        pk, p = self.pk(), self.prover
+        n_z = (1 << pk.log_domain) - 1
+        return {"a_g1": G1Points.view(p, pk.a_g1, pk.n_wires), "b_g1": G1Points.view(p, pk.b_g1, pk.n_wires),
+                "b_g2": G2Points.view(p, pk.b_g2, pk.n_wires), "k_g1": G1Points.view(p, pk.k_g1, pk.n_private),
+                "z_g1": G1Points.view(p, pk.z_g1, n_z),
+                "a_inf": flags_to_host(DeviceBuffer.view(p, pk.a_inf, (pk.n_wires + 7) // 8), pk.n_wires),
+                "b_inf": flags_to_host(DeviceBuffer.view(p, pk.b_inf, (pk.n_wires + 7) // 8), pk.n_wires)}
+
+    def free(self):
+        if self.handle:
+            self.prover.lib.cp_groth16_key_destroy(self.handle)
+            self.handle = None
 
 
 # ---- circuit files (N1) and the stored Groth16 proof form ----

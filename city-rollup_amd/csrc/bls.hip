@@ -10,3 +10,7 @@
 #include "groth16_pack.inc"
 #include "r1cs.h"
 #include "r1cs.inc"
+#include "fixed_base.h"
+#include "fixed_base.inc"
+#include "groth16_setup.h"
+#include "groth16_setup.inc"

@@ -471,7 +471,8 @@ void cp_ctx_destroy(cp_ctx *ctx) {
   // every owner of the context, between the synchronisation above and the destruction of the stream below (dev_mem.h, rule 2)
   ctx->pow_tables.clear(); ctx->prescale_tables.clear(); ctx->l0_tables.clear(); ctx->air_sel_tables.clear(); ctx->fr_twiddles.clear();
   ctx->arena.chunks.clear();
-  for (DevBuf *b : {&ctx->scratch, &ctx->wires_stage, &ctx->fr_work, &ctx->fr_pow[0].tab, &ctx->fr_pow[1].tab, &ctx->msm_ws}) b->reset();
+  for (DevBuf *b : {&ctx->scratch, &ctx->wires_stage, &ctx->fr_work, &ctx->fr_pow[0].tab, &ctx->fr_pow[1].tab, &ctx->msm_ws,
+                     &ctx->fixed_base[0].tab, &ctx->fixed_base[1].tab}) b->reset();
   ctx->pin.reset();
   ctx->noncanonical_flag.reset();
   if (ctx->stream) hipStreamDestroy(ctx->stream);

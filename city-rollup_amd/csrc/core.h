@@ -110,6 +110,11 @@ struct cp_ctx {
     uint64_t shift[4] = {0, 0, 0, 0};
   } fr_pow[2] = {{buf()}, {buf()}};  // [0]: forward (powers of the shift), [1]: inverse (powers of its inverse)
   DevBuf msm_ws = buf();  // grow-only workspace of the MSMs (counts, sorted indices, buckets)
+  struct FixedBase {        // cached window table of the fixed-base multiplication (fixed_base.inc): a setup asks for one base per group
+    DevBuf tab;
+    bool valid = false;
+    uint64_t base[24] = {};  // affine canonical coordinates as given at the API (12 words for G1)
+  } fixed_base[2] = {{buf()}, {buf()}};  // [0]: G1, [1]: G2
   // device staging buffer for wire matrices that arrive in host memory (cp_prove / cp_prove_batch_host)
   DevBuf wires_stage = buf();
   // per-proof workspace arena (prover_tail.inc): chunks survive between proofs

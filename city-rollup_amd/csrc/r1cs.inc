@@ -29,13 +29,43 @@ void r1cs_free(cp_r1cs_bls12381 *h) {
   delete h;
 }
 
-int r1cs_build(cp_ctx *ctx, const cp_r1cs_desc *desc, cp_r1cs_bls12381 *h) {
+// every refusal of a system, in the order it is read; host work alone (the Groth16 setup refuses a system before it stages anything)
+int r1cs_validate(cp_ctx *ctx, const cp_r1cs_desc *desc) {
   const size_t n = desc->n_constraints;
   if (n == 0 || n > ((size_t)1 << 28)) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: n_constraints %zu out of range (1 .. 2^28)", n);
   if (desc->n_wires == 0 || desc->n_wires > 0xffffffffull) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: n_wires %zu out of range (1 .. 2^32 - 1)", desc->n_wires);
   if (desc->n_coeffs >= r1cs::MAX_COEFFS) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: n_coeffs %zu out of range (below 2^29)", desc->n_coeffs);
   if (desc->n_coeffs && !desc->coeffs) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: coeffs is NULL with n_coeffs = %zu", desc->n_coeffs);
   if (desc->flags & ~CP_R1CS_NO_TERM_CLASSES) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: unknown flags 0x%x", desc->flags);
+  std::vector<uint8_t> canonical(desc->n_coeffs), used(desc->n_coeffs, 0);
+  for (size_t k = 0; k < desc->n_coeffs; k++) canonical[k] = blsfr::fr_is_canonical((const uint32_t *)(desc->coeffs + 4 * k));
+  const cp_r1cs_matrix *mats[3] = {&desc->a, &desc->b, &desc->c};
+  for (int m = 0; m < 3; m++) {
+    const cp_r1cs_matrix &M = *mats[m];
+    const char name = "ABC"[m];
+    if (!M.row_ptr) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c: row_ptr is NULL", name);
+    if (M.row_ptr[0] != 0) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row 0: row_ptr starts at %llu, not 0", name, (unsigned long long)M.row_ptr[0]);
+    for (size_t j = 0; j < n; j++)
+      if (M.row_ptr[j + 1] < M.row_ptr[j]) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: row_ptr decreases (%llu after %llu)", name, j, (unsigned long long)M.row_ptr[j + 1], (unsigned long long)M.row_ptr[j]);
+    const size_t nnz = M.row_ptr[n];
+    if (nnz && (!M.col || !M.coeff)) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c: col / coeff is NULL with %zu terms", name, nnz);
+    for (size_t j = 0; j < n; j++)
+      for (size_t t = M.row_ptr[j]; t < M.row_ptr[j + 1]; t++) {
+        const uint32_t col = M.col[t], k = M.coeff[t];
+        if (col >= desc->n_wires) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: wire %u >= n_wires %zu", name, j, col, desc->n_wires);
+        if (k >= desc->n_coeffs) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: coefficient index %u >= n_coeffs %zu", name, j, k, desc->n_coeffs);
+        if (!canonical[k]) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: coefficient %u is not canonical (>= r)", name, j, k);
+        used[k] = 1;
+      }
+  }
+  for (size_t k = 0; k < desc->n_coeffs; k++)
+    if (!canonical[k] && !used[k]) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: coefficient %zu is not canonical (>= r); no term uses it", k);
+  return CP_OK;
+}
+
+int r1cs_build(cp_ctx *ctx, const cp_r1cs_desc *desc, cp_r1cs_bls12381 *h) {
+  CP_TRY(r1cs_validate(ctx, desc));
+  const size_t n = desc->n_constraints;
   const bool classes = !(desc->flags & CP_R1CS_NO_TERM_CLASSES);
   int log_domain = 0;
   while (((size_t)1 << log_domain) < n) log_domain++;
@@ -46,11 +76,9 @@ int r1cs_build(cp_ctx *ctx, const cp_r1cs_desc *desc, cp_r1cs_bls12381 *h) {
   h->info.long_row_threshold = r1cs::LONG_ROW_THRESHOLD;
   // the coefficient table: class, one-limb constant, Montgomery form
   std::vector<uint32_t> cls(desc->n_coeffs), small(desc->n_coeffs);
-  std::vector<uint8_t> used(desc->n_coeffs, 0);
   std::vector<blsfr::Fr> mont(desc->n_coeffs);
   for (size_t k = 0; k < desc->n_coeffs; k++) {
     cls[k] = r1cs::classify(desc->coeffs + 4 * k, &small[k]);
-    if (cls[k] == r1cs::CLS_NOT_CANONICAL) { mont[k] = blsfr::fr_zero(); continue; }
     mont[k] = blsfr::fr_from_canonical((const uint32_t *)(desc->coeffs + 4 * k));
     if (!classes) cls[k] = r1cs::CLS_GENERAL;
   }
@@ -58,13 +86,7 @@ int r1cs_build(cp_ctx *ctx, const cp_r1cs_desc *desc, cp_r1cs_bls12381 *h) {
   std::vector<uint32_t> long_rows;
   for (int m = 0; m < 3; m++) {
     const cp_r1cs_matrix &M = *mats[m];
-    const char name = "ABC"[m];
-    if (!M.row_ptr) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c: row_ptr is NULL", name);
-    if (M.row_ptr[0] != 0) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row 0: row_ptr starts at %llu, not 0", name, (unsigned long long)M.row_ptr[0]);
-    for (size_t j = 0; j < n; j++)
-      if (M.row_ptr[j + 1] < M.row_ptr[j]) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: row_ptr decreases (%llu after %llu)", name, j, (unsigned long long)M.row_ptr[j + 1], (unsigned long long)M.row_ptr[j]);
     const size_t nnz = M.row_ptr[n];
-    if (nnz && (!M.col || !M.coeff)) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c: col / coeff is NULL with %zu terms", name, nnz);
     h->info.nnz[m] = nnz;
     std::vector<uint64_t> row_ptr(n + 1);
     std::vector<r1cs::Term> terms;
@@ -75,13 +97,7 @@ int r1cs_build(cp_ctx *ctx, const cp_r1cs_desc *desc, cp_r1cs_bls12381 *h) {
       for (uint32_t pass = 0; pass < r1cs::N_CLS; pass++)
         for (size_t t = M.row_ptr[j]; t < M.row_ptr[j + 1]; t++) {
           const uint32_t col = M.col[t], k = M.coeff[t];
-          if (pass == 0) {
-            if (col >= desc->n_wires) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: wire %u >= n_wires %zu", name, j, col, desc->n_wires);
-            if (k >= desc->n_coeffs) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: coefficient index %u >= n_coeffs %zu", name, j, k, desc->n_coeffs);
-            if (cls[k] == r1cs::CLS_NOT_CANONICAL) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS matrix %c row %zu: coefficient %u is not canonical (>= r)", name, j, k);
-            used[k] = 1;
-            if (cls[k] == r1cs::CLS_ZERO) h->info.n_terms_class[0]++;
-          }
+          if (pass == 0 && cls[k] == r1cs::CLS_ZERO) h->info.n_terms_class[0]++;
           if (cls[k] != pass) continue;
           h->info.n_terms_class[1 + pass]++;
           const uint32_t payload = pass == r1cs::CLS_GENERAL ? k : small[k];
@@ -95,8 +111,6 @@ int r1cs_build(cp_ctx *ctx, const cp_r1cs_desc *desc, cp_r1cs_bls12381 *h) {
     CP_TRY(r1cs_upload(ctx, h, row_ptr, &h->sys.m[m].row_ptr));
     CP_TRY(r1cs_upload(ctx, h, terms, &h->sys.m[m].terms));
   }
-  for (size_t k = 0; k < desc->n_coeffs; k++)
-    if (cls[k] == r1cs::CLS_NOT_CANONICAL && !used[k]) return set_error(ctx, CP_ERR_INVALID_ARG, "R1CS: coefficient %zu is not canonical (>= r); no term uses it", k);
   CP_TRY(r1cs_upload(ctx, h, mont, &h->sys.coeffs));
   const uint32_t *lr = nullptr;
   CP_TRY(r1cs_upload(ctx, h, long_rows, &lr));  // ascending: matrices in order, rows in order

@@ -843,6 +843,58 @@ int cp_groth16_prove_r1cs_bls12381(cp_ctx *ctx, const cp_groth16_pk *pk, const c
                                    const uint64_t *witness_dev, const uint64_t r[4], const uint64_t s[4], uint64_t out_a[12],
                                    uint64_t out_b[24], uint64_t out_c[12]);
 
+/* ---- Batched fixed-base multiplication: n multiples of ONE point, on the device ----
+ * What a proving key is made of: out[i] = k_i * base for i < n, written in the library's internal affine form
+ * (CP_G1_AFFINE_BYTES / CP_G2_AFFINE_BYTES per point: what the *_prepare_dev calls write and the MSMs read), with
+ * points_inf_dev_out[i] = 1 where the multiple is the point at infinity. An entry flagged infinity holds the base itself: a
+ * valid curve point that every reader skips by its flag, never uninitialised memory. Scalars: 4 little-endian u64 each, any
+ * 256-bit integer, as for the MSMs. base: affine canonical coordinates; refused if it is not on the curve / twist (which
+ * also rules out infinity: it has no affine form) or if it has small order. Its table of window multiples (33 windows of
+ * 128 signed byte digits) is built on first use and kept by the context, per group, until another base is asked for.
+ * Refusals - a NULL argument, n = 0, a base off the curve, an array the runtime knows to live on another device than the
+ * context's - are a status and a message. Asynchronous on the context stream once the table exists. */
+int cp_fixed_base_mul_bls12381_g1_dev(cp_ctx *ctx, const uint64_t base_xy[12], const uint64_t *scalars_dev, size_t n,
+                                      void *points_mont_dev_out, uint8_t *points_inf_dev_out);
+int cp_fixed_base_mul_bls12381_g2_dev(cp_ctx *ctx, const uint64_t base_xy[24], const uint64_t *scalars_dev, size_t n,
+                                      void *points_mont_dev_out, uint8_t *points_inf_dev_out);
+
+/* ---- Groth16 setup: (constraint system, trapdoor) -> proving key on the device + verifying key ----
+ * The step the reference takes once per circuit before its first wrap (`gnark_plonky2_wrapper::initialize`,
+ * city_rollup_core_worker/src/lib.rs:37-38 and :121-122; the verifying key comes back with every proof,
+ * city_rollup_circuit/src/worker/toolbox/root.rs:296). The library draws no randomness: the five scalars are the
+ * caller's, each canonical and non-zero. n_public counts wire 0 (the constant one): the wire order of cp_groth16_pk. The
+ * domain is 2^L with the log_domain L that cp_r1cs_bls12381_create computes for the same system; rows from n_constraints
+ * on are empty. With L_j the Lagrange basis of the domain, u_i = sum_j A[j][i] L_j(tau), v_i and w_i likewise from B and C:
+ *   a_g1[i] = [u_i]_1, b_g1[i] = [v_i]_1, b_g2[i] = [v_i]_2      a_inf / b_inf set where u_i / v_i = 0 (a wire that does not
+ *                                                                 occur in A / B: normal)
+ *   k_g1[i - n_public] = [(beta u_i + alpha v_i + w_i) / delta]_1 for the private wires
+ *   z_g1[j] = [tau^j (tau^(2^L) - 1) / delta]_1, j < 2^L - 1
+ *   ic[i] = [(beta u_i + alpha v_i + w_i) / gamma]_1 for the public wires (verifying key)
+ * over the standard generators. Refused with CP_ERR_INVALID_ARG (NULL + cp_last_error): a trapdoor scalar that is zero or
+ * >= r; tau^(2^L) = 1; n_public = 0 or > n_wires; a system of one constraint or of more than 2^28 wires; every refusal
+ * cp_r1cs_bls12381_create makes of the system, in its words; a private wire whose K logarithm is zero - in practice a
+ * private wire that occurs in no constraint - because cp_groth16_pk has no infinity flags for the K set (the message names
+ * the wire). A refused allocation is CP_ERR_OOM; either way the context stays usable and nothing is held.
+ * Parity with gnark's keys is unpinned (no key or circuit in the reference tree): the tests compare every point with
+ * [its logarithm] G computed from the trapdoor. */
+typedef struct cp_groth16_trapdoor { uint64_t tau[4], alpha[4], beta[4], gamma[4], delta[4]; } cp_groth16_trapdoor;
+typedef struct cp_groth16_vk {
+  uint64_t alpha_g1[12], beta_g2[24], gamma_g2[24], delta_g2[24];
+  size_t n_public; /* IC points, wire 0 included */
+} cp_groth16_vk;
+typedef struct cp_groth16_key cp_groth16_key;
+cp_groth16_key *cp_groth16_setup_bls12381(cp_ctx *ctx, const cp_r1cs_desc *system, size_t n_public,
+                                          const cp_groth16_trapdoor *trapdoor);
+/* The key owns its device arrays; it may be destroyed after its context. NULL is a no-op. */
+void cp_groth16_key_destroy(cp_groth16_key *key);
+/* A view of the proving key: the device pointers stay owned by the key and die with it. Any context of the key's device may
+ * prove with it. */
+int cp_groth16_key_pk(const cp_groth16_key *key, cp_groth16_pk *out);
+/* The verifying key. ic_xy_out: n_public x 12 u64 (affine canonical), ic_inf_out: n_public flags (1 = the point at infinity:
+ * a public wire that occurs in no constraint; its coordinates are then the generator's). Either may be NULL (not written):
+ * out->n_public says how much room the other call needs. */
+int cp_groth16_key_vk(const cp_groth16_key *key, cp_groth16_vk *out, uint64_t *ic_xy_out, uint8_t *ic_inf_out);
+
 
 /* The proof in the form the worker stores and the chain consumes: `CityGroth16ProofData { pi_a, pi_b_a0, pi_b_a1, pi_c }`
  * = 4 x 48 bytes (city_rollup_common/src/block_template/data.rs:6-34; produced at
