@@ -1111,6 +1111,79 @@ class Groth16Key:
             self.handle = None
 
 
+# ---- pairing products and the Groth16 verifier (GT values are e(P, Q)^3: include/cityprover.h) ----
+GT_WORDS = 72
+PAIRING_TRUSTED = 1
+ABI["cp_pairing_product_bls12381"] = (ctypes.c_int, [_vp, _u64p, _u8p, _u64p, _u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint, _u64p, _u8p, _u8p])
+ABI["cp_groth16_verifier_create_bls12381"] = (_vp, [_vp, ctypes.POINTER(Groth16Vk), _u64p, _u8p])
+ABI["cp_groth16_verifier_destroy"] = (None, [_vp])
+ABI["cp_groth16_verify_bls12381"] = (ctypes.c_int, [_vp, _vp, _u64p, _u64p, ctypes.c_size_t, ctypes.c_uint, _u8p])
+
+
+def _u8_or_none(a):
+    return None if a is None else a.ctypes.data_as(_u8p)
+
+
+def pairing_product(prover, g1_xy, g2_xy, k=1, g1_inf=None, g2_inf=None, flags=0, want_gt=True):
+    """cp_pairing_product_bls12381. g1_xy: (n_products * k, 12) u64, g2_xy: (n_products * k, 24) u64, affine canonical; the
+    optional flags are uint8 arrays of n_products * k. Returns (gt, is_one, status): gt is (n_products, 72) u64 or None."""
+    g1_xy, g2_xy = _as_u64(g1_xy).reshape(-1, 12), _as_u64(g2_xy).reshape(-1, 24)
+    assert len(g1_xy) == len(g2_xy) and k >= 1 and len(g1_xy) % k == 0
+    n = len(g1_xy) // k
+    f1 = None if g1_inf is None else np.ascontiguousarray(g1_inf, np.uint8)
+    f2 = None if g2_inf is None else np.ascontiguousarray(g2_inf, np.uint8)
+    gt = np.zeros((n, GT_WORDS), np.uint64) if want_gt else None
+    is_one, status = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    prover._check(prover.lib.cp_pairing_product_bls12381(prover.ctx, _ptr(g1_xy), _u8_or_none(f1), _ptr(g2_xy), _u8_or_none(f2), n, k, flags,
+                                                         None if gt is None else _ptr(gt), _u8_or_none(is_one), _u8_or_none(status)))
+    return gt, is_one, status
+
+
+class Groth16Verifier:
+    """The verifier of one verifying key, resident on the device (cp_groth16_verifier_create_bls12381)."""
+
+    def __init__(self, prover, handle, n_public):
+        self.prover, self.handle, self.n_public = prover, handle, n_public
+
+    @classmethod
+    def create(cls, prover, vk, ic_xy, ic_inf=None):
+        """vk: Groth16Vk; ic_xy: (n_public, 12) u64; ic_inf: n_public flags or None"""
+        ic_xy = _as_u64(ic_xy).reshape(-1, 12)
+        inf = None if ic_inf is None else np.ascontiguousarray(ic_inf, np.uint8)
+        handle = prover.lib.cp_groth16_verifier_create_bls12381(prover.ctx, ctypes.byref(vk), _ptr(ic_xy), _u8_or_none(inf))
+        if not handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+        return cls(prover, handle, int(vk.n_public))
+
+    @classmethod
+    def from_key(cls, prover, key):
+        """from a Groth16Key (cp_groth16_key_vk)"""
+        vk = Groth16Vk()
+        prover._check(prover.lib.cp_groth16_key_vk(key.handle, ctypes.byref(vk), None, None))
+        xy, inf = np.zeros((vk.n_public, 12), np.uint64), np.zeros(vk.n_public, np.uint8)
+        prover._check(prover.lib.cp_groth16_key_vk(key.handle, ctypes.byref(vk), _ptr(xy), inf.ctypes.data_as(_u8p)))
+        return cls.create(prover, vk, xy, inf)
+
+    def verify(self, proofs, publics=None, flags=0, prover=None):
+        """proofs: (n, 48) u64, A | B | C; publics: (n, n_public - 1, 4) u64 (None when the key has no public input beside wire 0).
+        Returns the n verdicts as uint8: 0 accepted, 1 rejected, 2 bad point, 3 outside the subgroup, 4 public input >= r.
+        prover: another context of the same device (default: the one the verifier was made with)."""
+        p = prover or self.prover
+        proofs = _as_u64(proofs).reshape(-1, 48)
+        n = len(proofs)
+        pub = None
+        if self.n_public > 1:
+            pub = _as_u64(publics).reshape(n, self.n_public - 1, 4)
+        out = np.zeros(n, np.uint8)
+        p._check(p.lib.cp_groth16_verify_bls12381(p.ctx, self.handle, _ptr(proofs), None if pub is None else _ptr(pub), n, flags, out.ctypes.data_as(_u8p)))
+        return out
+
+    def close(self):
+        if self.handle:
+            self.prover.lib.cp_groth16_verifier_destroy(self.handle)
+            self.handle = None
+
+
 # ---- circuit files (N1) and the stored Groth16 proof form ----
 ABI["cp_circuit_load_file"] = (_vp, [_vp, ctypes.c_char_p])
 ABI["cp_circuit_save_file"] = (ctypes.c_int, [_vp, ctypes.c_char_p])

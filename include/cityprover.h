@@ -895,6 +895,51 @@ int cp_groth16_key_pk(const cp_groth16_key *key, cp_groth16_pk *out);
  * out->n_public says how much room the other call needs. */
 int cp_groth16_key_vk(const cp_groth16_key *key, cp_groth16_vk *out, uint64_t *ic_xy_out, uint8_t *ic_inf_out);
 
+/* ---- BLS12-381 pairing products and the Groth16 verifier, batched on the device ----
+ * The optimal-ate pairing e: G1 x G2 -> GT, raised to a fixed power: every GT value of this library is
+ * e(P, Q)^c with c = 3 (the hard part of the final exponentiation computes f^(3 (p^4 - p^2 + 1) / r); 3 is coprime to r, so
+ * "equals one" and every equation between products keep their meaning). A GT value is CP_GT_WORDS u64: the 12 F_p
+ * coefficients, canonical, 6 little-endian u64 each, of an element of F_p^12 = F_p^2[w] / (w^6 - (1 + u)) in the order
+ * w^0.c0, w^0.c1, w^1.c0, ..., w^5.c1 (the tower F_p^6 = F_p^2[v] / (v^3 - (1 + u)), F_p^12 = F_p^6[w] / (w^2 - v) with
+ * v = w^2: the even powers are the F_p^6 part c0, the odd powers c1). The layout is this library's own: the tree holds no
+ * pairing vector of another library to match.
+ *
+ * cp_pairing_product_bls12381: n_products products of k pairings each. Pair j of product i is point i k + j of both arrays
+ * (affine canonical: 12 u64 for G1, 24 for G2: x.c0, x.c1, y.c0, y.c1); a pair with either infinity flag set contributes
+ * the identity and its coordinates are not looked at. Per product: status 0 ok, 1 a coordinate >= p, 2 a point not on the
+ * curve / twist, 3 a point outside the r-torsion ([r]P != infinity; skipped with CP_PAIRING_TRUSTED, and then the result
+ * for such a point is unspecified) - the first of these met in the order G1 then G2 of pair 0, pair 1, .... A product whose
+ * status is not 0 has is_one = 0 and an all-zero GT value; the call still returns CP_OK: a bad point is a verdict on its
+ * item. gt_out_host, is_one_out_host, status_out_host may each be NULL, but not both of the first two.
+ * CP_ERR_INVALID_ARG: a NULL point array, n_products = 0, k = 0, both outputs NULL, unknown flag bits. A refused
+ * allocation is CP_ERR_OOM and the context stays usable. One lane per pair runs a Miller loop, one lane per product
+ * multiplies its k values and runs the final exponentiation: the call is made for batches (a lone pairing takes tens of
+ * milliseconds). */
+#define CP_GT_WORDS 72
+#define CP_PAIRING_TRUSTED 1u
+int cp_pairing_product_bls12381(cp_ctx *ctx, const uint64_t *g1_xy_host, const uint8_t *g1_inf_host,
+                                const uint64_t *g2_xy_host, const uint8_t *g2_inf_host, size_t n_products, size_t k,
+                                unsigned flags, uint64_t *gt_out_host, uint8_t *is_one_out_host, uint8_t *status_out_host);
+
+/* The Groth16 verifier of a verifying key: e(A, B) = e(alpha, beta) e(L, gamma) e(C, delta), L = IC_0 + sum_i x_i IC_i.
+ * create: vk and the IC points with their flags as cp_groth16_key_vk returns them. Every key point is checked for the
+ * curve and the r-torsion, always (NULL + cp_last_error naming the point); e(alpha, beta)^c is computed once; the IC
+ * points, -gamma and -delta are held on the context's device. Any context of that device may verify with it, and it may be
+ * destroyed after its context. NULL + CP_ERR_OOM for a refused allocation.
+ * verify: proofs_host: n_proofs x 48 u64, A (12) | B (24) | C (12), affine canonical, as the provers return them (affine
+ * input cannot express infinity: all-zero coordinates fail the curve check). public_inputs_host: n_proofs x
+ * (n_public - 1) x 4 u64, wires 1 .. n_public - 1 (wire 0 is the constant one); may be NULL when n_public = 1.
+ * verdict_out_host, per proof: 0 accepted, 1 the equation does not hold, 2 a coordinate >= p or a point off the curve /
+ * twist, 3 a point outside the r-torsion (not checked with CP_PAIRING_TRUSTED), 4 a public input >= r; of several, the
+ * largest of 2, 3, 4 that applies. The call returns CP_OK whatever the verdicts. */
+typedef struct cp_groth16_verifier cp_groth16_verifier;
+cp_groth16_verifier *cp_groth16_verifier_create_bls12381(cp_ctx *ctx, const cp_groth16_vk *vk, const uint64_t *ic_xy,
+                                                         const uint8_t *ic_inf);
+void cp_groth16_verifier_destroy(cp_groth16_verifier *v);
+int cp_groth16_verify_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint64_t *proofs_host,
+                               const uint64_t *public_inputs_host, size_t n_proofs, unsigned flags,
+                               uint8_t *verdict_out_host);
+
 
 /* The proof in the form the worker stores and the chain consumes: `CityGroth16ProofData { pi_a, pi_b_a0, pi_b_a1, pi_c }`
  * = 4 x 48 bytes (city_rollup_common/src/block_template/data.rs:6-34; produced at
