@@ -248,6 +248,11 @@ typedef struct {
   uint64_t k_is[256]; /* num_routed_wires coset shifts */
 } or_gates;
 int or_gates_num_constraints(const or_gates *g);
+/* TEST ONLY (tests/test_gate_semantics.py): the UNFILTERED constraints of one gate on n_rows rows, all values in F_p^2 as
+ * (c0, c1) word pairs. consts: [n_rows][num_consts], the gate's local constants after the selectors; wires: [n_rows][num_wires];
+ * pi_hash: 4 values; out: [n_rows][count]. Returns the gate's constraint count (0 for Noop), -1 for an unknown gate. */
+int or_gate_row_constraints(const or_gate *g, const uint64_t *consts, int num_consts, const uint64_t *wires, int num_wires,
+                            const uint64_t *pi_hash, size_t n_rows, uint64_t *out);
 /* A8: quotient chunk polynomials (coefficients), num_challenges*quotient_degree_factor x n, from the
  * bit-reversed LDEs of the three oracles. */
 int or_quotient_polys(const or_shape *sh, const or_gates *G, const uint64_t pi_hash[4], const uint64_t *cs_lde,

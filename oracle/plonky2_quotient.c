@@ -217,6 +217,19 @@ static void gate_eval(const or_gate *g, const gl2_t *consts, const gl2_t *wires,
   }
 }
 
+int or_gate_row_constraints(const or_gate *g, const uint64_t *consts, int num_consts, const uint64_t *wires, int num_wires,
+                            const uint64_t *pi_hash, size_t n_rows, uint64_t *out) {
+  const int c = gate_num_constraints(g);
+  if (c < 0 || c > 512) return -1;
+  gl2_t tmp[512];
+  for (size_t r = 0; r < n_rows; r++) {
+    gate_eval(g, (const gl2_t *)consts + r * (size_t)num_consts, (const gl2_t *)wires + r * (size_t)num_wires,
+              (const gl2_t *)pi_hash, tmp);
+    memcpy(out + r * (size_t)c * 2, tmp, (size_t)c * sizeof(gl2_t));
+  }
+  return c;
+}
+
 /* filter of gate `row` inside its selector group: prod_{i in group, i != row} (i - s) [* (UNUSED - s)] */
 static gl2_t gate_filter(int row, const or_gate *g, gl2_t s, int many_selectors) {
   gl2_t f = gl2_from_base(1);

@@ -350,6 +350,24 @@ def verify_full(shape, gates, circuit_digest, cs_cap, proof_bytes):
                               ptr(flat("quotient_polys")), ptr(arr(list(dbg.betas)[:nc])),
                               ptr(arr(list(dbg.gammas)[:nc])), ptr(arr(list(dbg.alphas)[:nc])))
     return 0 if rc == 0 else -1000 + rc
+
+
+def gate_row_constraints(gate, consts, wires, pi_hash):
+    """or_gate_row_constraints (test-only export): the unfiltered constraints of one gate (type, param, param2, param3) on n rows.
+    consts [n][k][2], wires [n][W][2], pi_hash [4][2], all uint64 F_p^2 word pairs -> [n][count][2]."""
+    L = lib()
+    L.or_gate_row_constraints.restype = ctypes.c_int
+    g = Gate(gate[0], 0, 0, 1, gate[1], gate[2], gate[3])
+    consts, wires, pi_hash = arr(consts), arr(wires), arr(pi_hash)
+    n = wires.shape[0]
+    assert wires.ndim == 3 and wires.shape[2] == 2 and consts.shape[0] == n and consts.shape[2] == 2 and pi_hash.shape == (4, 2)
+    out = np.zeros((n, 512, 2), np.uint64)
+    cnt = L.or_gate_row_constraints(ctypes.byref(g), ptr(consts), ctypes.c_int(consts.shape[1]), ptr(wires),
+                                    ctypes.c_int(wires.shape[1]), ptr(pi_hash), ctypes.c_size_t(n), ptr(out))
+    assert 0 <= cnt <= 512, cnt
+    return out.reshape(-1)[:n * cnt * 2].reshape(n, cnt, 2).copy()
+
+
 GATE_POSEIDON = 4
 GATE_COMPARISON, GATE_U32_ARITHMETIC, GATE_U32_RANGE_CHECK = 5, 6, 7
 GATE_U32_ADD_MANY, GATE_U32_SUBTRACTION, GATE_U32_INTERLEAVE, GATE_UNINTERLEAVE_TO_U32, GATE_UNINTERLEAVE_TO_B32 = 8, 9, 10, 11, 12

@@ -258,6 +258,55 @@ def uninterleave_row(rng, num_ops, to_b32):
     return routed + bits
 
 
+def gate_row(wrng, gate, k0, k1, pi_hash):
+    """One satisfying row of `gate` = (type, param, param2, param3) from this file's generators, drawing from wrng; k0, k1 are the
+    row's two constants. None for Noop (no wires) and Poseidon (build_gate_set fills those in one batch through its backend)."""
+    t, a, b, c = gate
+    row = None
+    if t == PUBLIC_INPUT:
+        row = pi_hash
+    elif t == CONSTANT:
+        row = [k0, k1][:a]
+    elif t == ARITHMETIC:
+        row = arithmetic_row(wrng, a, k0, k1)
+    elif t == ARITHMETIC_EXT:
+        row = arithmetic_ext_row(wrng, a, k0, k1)
+    elif t == MUL_EXT:
+        row = mul_ext_row(wrng, a, k0)
+    elif t == BASE_SUM:
+        row = base_sum_row(wrng, a, b)
+    elif t == RANDOM_ACCESS:
+        row = random_access_row(wrng, a, b, c, [k0, k1])
+    elif t == REDUCING:
+        row = reducing_row(wrng, a, False)
+    elif t == REDUCING_EXT:
+        row = reducing_row(wrng, a, True)
+    elif t == POSEIDON_MDS:
+        row = poseidon_mds_row(wrng)
+    elif t == COSET_INTERPOLATION:
+        row = coset_interpolation_row(wrng, a, b)
+    elif t == EXPONENTIATION:
+        row = exponentiation_row(wrng, a)
+    elif t == COMPARISON:
+        x, y = int(wrng.integers(0, 2**a)), int(wrng.integers(0, 2**a))
+        row = comparison_row(x, x if wrng.random() < 0.2 else y, a, b)
+    elif t == U32_ARITHMETIC:
+        row = u32_arithmetic_row([tuple(int(v) for v in wrng.integers(0, 2**32, 3)) for _ in range(a)])
+    elif t == U32_RANGE_CHECK:
+        row = u32_range_check_row([int(v) for v in wrng.integers(0, 2**32, a)])
+    elif t == U32_ADD_MANY:
+        row = add_many_row(wrng, a, b)
+    elif t == U32_SUBTRACTION:
+        row = subtraction_row(wrng, a)
+    elif t == U32_INTERLEAVE:
+        row = interleave_row(wrng, a)
+    elif t == UNINTERLEAVE_TO_U32:
+        row = uninterleave_row(wrng, a, False)
+    elif t == UNINTERLEAVE_TO_B32:
+        row = uninterleave_row(wrng, a, True)
+    return row
+
+
 def build_gate_set(gate_set=CITY_COMMON, db=7, num_routed=80, num_wires=135, chunk=8, nc=2, seed=0, rate_bits=3,
                    cap_height=2, pow_bits=5, num_query_rounds=4, arity_bits=(2,), n_copies=8, weights=None,
                    noop_fraction=0.1, backend=None, witness_seed=None):
@@ -320,49 +369,7 @@ def build_gate_set(gate_set=CITY_COMMON, db=7, num_routed=80, num_wires=135, chu
     params = {g[0]: g for g in gates}
     for i, t in enumerate(types):
         _, a, b, c = params[t]
-        k0, k1 = int(c0[i]), int(c1[i])
-        row = None
-        if t == PUBLIC_INPUT:
-            row = pi_hash
-        elif t == CONSTANT:
-            row = [k0, k1][:a]
-        elif t == ARITHMETIC:
-            row = arithmetic_row(wrng, a, k0, k1)
-        elif t == ARITHMETIC_EXT:
-            row = arithmetic_ext_row(wrng, a, k0, k1)
-        elif t == MUL_EXT:
-            row = mul_ext_row(wrng, a, k0)
-        elif t == BASE_SUM:
-            row = base_sum_row(wrng, a, b)
-        elif t == RANDOM_ACCESS:
-            row = random_access_row(wrng, a, b, c, [k0, k1])
-        elif t == REDUCING:
-            row = reducing_row(wrng, a, False)
-        elif t == REDUCING_EXT:
-            row = reducing_row(wrng, a, True)
-        elif t == POSEIDON_MDS:
-            row = poseidon_mds_row(wrng)
-        elif t == COSET_INTERPOLATION:
-            row = coset_interpolation_row(wrng, a, b)
-        elif t == EXPONENTIATION:
-            row = exponentiation_row(wrng, a)
-        elif t == COMPARISON:
-            x, y = int(wrng.integers(0, 2**a)), int(wrng.integers(0, 2**a))
-            row = comparison_row(x, x if wrng.random() < 0.2 else y, a, b)
-        elif t == U32_ARITHMETIC:
-            row = u32_arithmetic_row([tuple(int(v) for v in wrng.integers(0, 2**32, 3)) for _ in range(a)])
-        elif t == U32_RANGE_CHECK:
-            row = u32_range_check_row([int(v) for v in wrng.integers(0, 2**32, a)])
-        elif t == U32_ADD_MANY:
-            row = add_many_row(wrng, a, b)
-        elif t == U32_SUBTRACTION:
-            row = subtraction_row(wrng, a)
-        elif t == U32_INTERLEAVE:
-            row = interleave_row(wrng, a)
-        elif t == UNINTERLEAVE_TO_U32:
-            row = uninterleave_row(wrng, a, False)
-        elif t == UNINTERLEAVE_TO_B32:
-            row = uninterleave_row(wrng, a, True)
+        row = gate_row(wrng, params[t], int(c0[i]), int(c1[i]), pi_hash)
         if row is not None:
             assert len(row) == gate_num_wires(params[t]), (t, len(row))
             wires[:len(row), i] = np.array(row, dtype=np.uint64)
