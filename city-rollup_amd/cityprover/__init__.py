@@ -1283,6 +1283,47 @@ def verify_fri_queries_with_challenges(shape, proof_bytes, alpha, zeta, fri_beta
         raise CityProverError(f"[{rc}] " + lib.cp_last_error(None).decode())
 
 
+# ---- batches of proofs of one circuit: the query phase on the device (cp_verify_batch) ----
+_u8pp = ctypes.POINTER(ctypes.c_char_p)
+_szp = ctypes.POINTER(ctypes.c_size_t)
+ABI["cp_verify_batch"] = (ctypes.c_int, [_vp, _u8pp, _szp, ctypes.c_size_t, ctypes.c_size_t, _vp])
+ABI["cp_verify_fri_queries_with_challenges_batch"] = (ctypes.c_int, [_vp, ctypes.POINTER(Shape), _u64p, _u8pp, _szp, ctypes.c_size_t, _u64p, _u64p,
+                                                                     _u64p, _u64p, ctypes.c_size_t, _vp])
+# cp_verify_verdict; status: 0 accepted, 1 malformed, 2 element >= p, 3 public inputs, 4 zeta in the subgroup / opening point on the
+# coset, 5 vanishing identity, 6 proof of work, 7 oracle path, 8 FRI layer value, 9 FRI layer path, 10 final polynomial
+VERDICT = np.dtype([("status", np.int32), ("query", np.int32), ("detail", np.int32), ("reserved", np.int32)])
+
+
+def _proof_array(proofs):
+    proofs = [bytes(b) for b in proofs]
+    ptrs = (ctypes.c_char_p * max(len(proofs), 1))(*proofs)
+    lens = (ctypes.c_size_t * max(len(proofs), 1))(*[len(b) for b in proofs])
+    return proofs, ptrs, lens
+
+
+def verify_batch(circuit, proofs, chunk=0):
+    """cp_verify_batch: one verdict per proof (structured array, dtype VERDICT); raises only for a call that could not run."""
+    keep, ptrs, lens = _proof_array(proofs)
+    out = np.zeros(len(keep), VERDICT)
+    p = circuit.prover
+    p._check(p.lib.cp_verify_batch(circuit.handle, ptrs, lens, len(keep), int(chunk), out.ctypes.data))
+    return out
+
+
+def verify_fri_queries_with_challenges_batch(prover, shape, proofs, alphas, zetas, fri_betas, x_indices, cs_cap=None, chunk=0):
+    """cp_verify_fri_queries_with_challenges_batch: the device twin of verify_fri_queries_with_challenges for n proofs of one
+    shape. alphas, zetas: (n, 2); fri_betas: (n, n_arity, 2); x_indices: (n, num_query_rounds). Returns the verdicts."""
+    keep, ptrs, lens = _proof_array(proofs)
+    n = len(keep)
+    a, z, fb, xi = _as_u64(alphas).reshape(-1), _as_u64(zetas).reshape(-1), _as_u64(fri_betas).reshape(-1), _as_u64(x_indices).reshape(-1)
+    cap = None if cs_cap is None else _as_u64(cs_cap).reshape(-1)
+    out = np.zeros(n, VERDICT)
+    prover._check(prover.lib.cp_verify_fri_queries_with_challenges_batch(
+        prover.ctx, ctypes.byref(shape), None if cap is None else _ptr(cap), ptrs, lens, n, _ptr(a) if a.size else None, _ptr(z) if z.size else None,
+        _ptr(fb) if fb.size else None, _ptr(xi) if xi.size else None, int(chunk), out.ctypes.data))
+    return out
+
+
 def fri_combine(prover, polys, alpha):
     """sum_j alpha^j polys[j] over F_p^2 on the GPU (cp_fri_combine_dev). polys: (k, n) uint64 -> (n, 2) uint64."""
     f = _as_u64(polys)

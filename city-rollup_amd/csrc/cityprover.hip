@@ -925,6 +925,7 @@ int cp_commit_dev(cp_ctx *ctx, const uint64_t *values, size_t k, int log_n, int 
 #include "quotient.inc"
 #include "prover_tail.inc"
 #include "batcher.inc"
+#include "fri_verify.h"
 #include "verify.inc"
 #include "fri_prove.inc"
 #include "circuit_file.inc"

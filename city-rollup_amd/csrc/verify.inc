@@ -507,3 +507,332 @@ extern "C" int cp_verify_fri_queries_with_challenges(const cp_shape *shape, cons
   if (pp.n_pi != (size_t)sh.num_public_inputs) return set_error(nullptr, CP_ERR_VERIFY, "%zu public inputs, the shape says %d", pp.n_pi, sh.num_public_inputs);
   return verify_queries(nullptr, sh, proof, proof_len, pp, gl::Ext{alpha[0], alpha[1]}, gl::Ext{zeta[0], zeta[1]}, fb.data(), x_indices);
 } CP_CATCH(nullptr)
+
+// ---- batches of proofs of one shape: the query phase on the device (fri_verify.h) ------------------------------------------
+namespace {
+
+// Staged proof bytes per device pass when the caller leaves chunk_proofs 0 (include/cityprover.h says so too)
+constexpr size_t VERIFY_BATCH_PASS_BYTES = (size_t)64 << 20;
+
+// The word offsets of bincode `FriProof` starting at word `o`, field by field as parse_fri_proof walks it; returns the word
+// behind the proof-of-work witness. D's oracle caps (cap_src, cap_off) are the caller's.
+size_t friv_layout(const FriVerifyInstance &I, size_t o, friv::Instance &D) {
+  const FriCfg &c = I.cfg;
+  const int lb = I.db + c.rate_bits;
+  const size_t cap_n = (size_t)1 << c.cap_height;
+  D.n_oracles = (uint32_t)I.n_oracles; D.n_layers = (uint32_t)c.n_arity; D.n_queries = (uint32_t)c.num_query_rounds;
+  D.cap_height = (uint32_t)c.cap_height; D.log_n = (uint32_t)lb; D.depth0 = (uint32_t)(lb - c.cap_height);
+  D.omega = GL_ROOTS[lb];
+  o += 1;
+  for (int l = 0; l < c.n_arity; l++) { o += 1; D.fcap_off[l] = (uint32_t)o; o += cap_n * 4; }
+  o += 1;
+  D.q_base = (uint32_t)o;
+  size_t r = 1;
+  for (int b = 0; b < I.n_oracles; b++) {
+    D.leaf_len[b] = (uint32_t)I.leaf_len[b];
+    r += 1; D.leaf_off[b] = (uint32_t)r; r += I.leaf_len[b];
+    r += 1; D.sib_off[b] = (uint32_t)r; r += (size_t)D.depth0 * 4;
+  }
+  r += 1;
+  int bits = lb, total_arity = 0;
+  for (int l = 0; l < c.n_arity; l++) {
+    const int ab = c.arity_bits[l];
+    bits -= ab; total_arity += ab;
+    int depth = bits - c.cap_height;
+    if (depth < 0) depth = 0;
+    D.arity_bits[l] = (uint32_t)ab; D.layer_depth[l] = (uint32_t)depth; D.arity_g[l] = GL_ROOTS[ab];
+    r += 1; D.ev_off[l] = (uint32_t)r; r += (size_t)2 << ab;
+    r += 1; D.path_off[l] = (uint32_t)r; r += (size_t)depth * 4;
+  }
+  D.q_words = (uint32_t)r;
+  o += (size_t)c.num_query_rounds * r;
+  D.final_len = (uint32_t)(((size_t)1 << I.db) >> total_arity);
+  o += 1; D.final_off = (uint32_t)o; o += (size_t)D.final_len * 2;
+  return o + 1;
+}
+
+// plonky2's instance as the kernels read it: the table, and the length in words every proof of the shape has
+int plonky2_layout(cp_ctx *ctx, const cp_shape &sh, bool check_cs, friv::Instance &D, size_t &proof_words) {
+  FriVerifyInstance I;
+  plonky2_fri_instance(sh, nullptr, gl::Ext{0, 0}, I);
+  memset(&D, 0, sizeof D);
+  const size_t cap_n = (size_t)1 << sh.cap_height, nc = (size_t)sh.num_challenges;
+  size_t o = 0;
+  for (int b = 1; b <= 3; b++) { o += 1; D.cap_src[b] = 1; D.cap_off[b] = (uint32_t)o; o += cap_n * 4; }
+  D.cap_src[0] = check_cs ? 2 : 0;
+  const size_t cnt[9] = {(size_t)sh.num_constants, (size_t)sh.num_routed_wires, I.kk[1], nc, nc, I.kk[2] - nc, I.kk[3], 0, 0};
+  for (int i = 0; i < 9; i++) o += 1 + cnt[i] * 2;
+  const size_t fri_end = friv_layout(I, o, D);
+  proof_words = fri_end + 1 + (size_t)sh.num_public_inputs;
+  if (I.ranges.size() > (size_t)friv::MAX_BATCHES) return set_error(ctx, CP_ERR_INTERNAL, "too many opening batches");
+  D.n_batches = (uint32_t)I.ranges.size();
+  uint32_t nr = 0;
+  for (size_t b = 0; b < I.ranges.size(); b++) {
+    D.batch_first[b] = nr;
+    for (const cp_fri_poly_range &R : I.ranges[b]) {
+      if (nr >= (uint32_t)friv::MAX_RANGES) return set_error(ctx, CP_ERR_INTERNAL, "too many opening ranges");
+      D.r_oracle[nr] = R.oracle; D.r_first[nr] = R.first; D.r_count[nr] = R.count;
+      nr++;
+    }
+  }
+  D.batch_first[I.ranges.size()] = nr;
+  D.n_ranges = nr;
+  if (proof_words > ((size_t)1 << 31)) return set_error(ctx, CP_ERR_INVALID_ARG, "shape out of range");
+  return CP_OK;
+}
+
+// One proof's challenge record (fri_verify.h): what verify_fri_queries precomputes, and the challenges
+void fill_record(const FriVerifyInstance &I, gl::Ext alpha, const gl::Ext *fbetas, const uint64_t *x_indices, uint64_t *rec) {
+  const uint32_t nb = (uint32_t)I.points.size(), nl = (uint32_t)I.cfg.n_arity;
+  const uint64_t N = (uint64_t)1 << (I.db + I.cfg.rate_bits);
+  rec[friv::rec_alpha()] = alpha.a; rec[friv::rec_alpha() + 1] = alpha.b;
+  for (uint32_t b = 0; b < nb; b++) {
+    gl::Ext red{0, 0};
+    for (size_t j = I.opened[b].size(); j-- > 0;) red = gl::ext_add(gl::ext_mul(red, alpha), I.opened[b][j]);
+    const gl::Ext shift = host_ext_pow(alpha, (uint64_t)I.opened[b].size());
+    uint64_t *rb = rec + friv::rec_batch(b);
+    rb[0] = I.points[b].a; rb[1] = I.points[b].b; rb[2] = red.a; rb[3] = red.b; rb[4] = shift.a; rb[5] = shift.b;
+  }
+  for (uint32_t l = 0; l < nl; l++) { rec[friv::rec_beta(nb, l)] = fbetas[l].a; rec[friv::rec_beta(nb, l) + 1] = fbetas[l].b; }
+  for (int qi = 0; qi < I.cfg.num_query_rounds; qi++) rec[friv::rec_index(nb, nl, (uint32_t)qi)] = x_indices[qi] % N;
+}
+
+cp_verify_verdict verdict(int status, int query = -1, int detail = -1) { return cp_verify_verdict{status, query, detail, 0}; }
+// which of parse_proof_bytes' refusals this thread's last error is
+cp_verify_verdict parse_verdict() {
+  const char *m = g_tls_error.c_str();
+  return verdict(strstr(m, "malformed proof") ? 1 : strstr(m, "public inputs") ? 3 : 2);
+}
+cp_verify_verdict key_verdict(const friv::Instance &D, uint32_t key) {
+  if (key == friv::KEY_NONE) return verdict(0);
+  const int q = (int)(key >> 8);
+  const uint32_t ord = key & 0xFF, n_or = D.n_oracles;
+  if (ord < n_or) return verdict(7, q, (int)ord);
+  if (ord == friv::ord_coset(n_or)) return verdict(4, q);
+  if (ord == friv::ord_final(n_or, D.n_layers)) return verdict(10, q);
+  const uint32_t k = ord - n_or - 1;
+  return verdict(k & 1 ? 9 : 8, q, (int)(k >> 1));
+}
+
+// Everything cp_verify does before its query phase, for one proof of a batch, on whatever thread: the shape-directed parse, the
+// transcript, the vanishing identity at zeta, the FRI challenges and the proof of work - the same functions, in the same
+// order. ctx is never touched (errors go to the thread's own message). ks: the circuit's k_is, fetched once per call.
+// Status 0: `rec` holds the proof's challenge record and the query phase is the device's.
+cp_verify_verdict verify_host_phase(const cp_circuit &circ, const uint64_t *ks, const uint8_t *proof, size_t len, uint64_t *rec) {
+  const cp_shape &sh = circ.sh;
+  const int db = sh.degree_bits, nc = sh.num_challenges;
+  const size_t n = (size_t)1 << db, cap_n = (size_t)1 << sh.cap_height;
+  ParsedProof pp;
+  if (parse_proof_bytes(nullptr, sh, circ.cs.cap_host.data(), proof, len, pp) != CP_OK) return parse_verdict();
+  const uint64_t *const *caps = pp.caps, *const *op = pp.op;
+  const size_t *cnt = pp.cnt;
+  uint64_t pi_hash[4];
+  {
+    uint64_t st[12] = {0};
+    for (size_t off = 0; off < pp.n_pi; off += 8) {
+      size_t c = pp.n_pi - off < 8 ? pp.n_pi - off : 8;
+      memcpy(st, pp.pi + off, c * 8);
+      poseidon::permute_host(st);
+    }
+    memcpy(pi_hash, st, 32);
+  }
+  HostChallenger C;
+  C.observe(circ.digest, 4);
+  C.observe(pi_hash, 4);
+  C.observe(caps[1], cap_n * 4);
+  std::vector<uint64_t> betas(nc), gammas(nc), alphas(nc);
+  for (int i = 0; i < nc; i++) betas[i] = C.challenge();
+  for (int i = 0; i < nc; i++) gammas[i] = C.challenge();
+  C.observe(caps[2], cap_n * 4);
+  for (int i = 0; i < nc; i++) alphas[i] = C.challenge();
+  C.observe(caps[3], cap_n * 4);
+  const gl::Ext zeta = C.ext_challenge();
+  const int zorder[6] = {0, 1, 2, 3, 5, 6};
+  for (int i = 0; i < 6; i++) C.observe(op[zorder[i]], cnt[zorder[i]] * 2);
+  C.observe(op[4], cnt[4] * 2);
+  {
+    const gl::Ext zn = host_ext_pow(zeta, n);
+    const gl::Ext zh = gl::ext_sub(zn, ext(1));
+    if (zh.a == 0 && zh.b == 0) return verdict(4);
+    const gl::Ext l0 = gl::ext_mul(zh, host_ext_inv(gl::ext_scale(gl::ext_sub(zeta, ext(1)), (uint64_t)n % gl::P)));
+    std::vector<gl::Ext> van(nc);
+    host_vanishing(circ, pi_hash, zeta, l0, (const gl::Ext *)op[0], (const gl::Ext *)op[2], (const gl::Ext *)op[3], (const gl::Ext *)op[4],
+                   (const gl::Ext *)op[5], (const gl::Ext *)op[1], ks, betas.data(), gammas.data(), alphas.data(), van.data());
+    const int qdf = sh.quotient_degree_factor;
+    for (int c = 0; c < nc; c++) {
+      gl::Ext acc{0, 0};
+      for (int i = qdf - 1; i >= 0; i--)
+        acc = gl::ext_add(gl::ext_mul(acc, zn), gl::Ext{op[6][2 * (c * qdf + i)], op[6][2 * (c * qdf + i) + 1]});
+      if (!ext_eq(gl::ext_mul(acc, zh), van[c])) return verdict(5, -1, c);
+    }
+  }
+  FriVerifyInstance I;
+  plonky2_fri_instance(sh, &pp, zeta, I);
+  gl::Ext alpha;
+  std::vector<gl::Ext> fbetas;
+  std::vector<uint64_t> x_indices;
+  if (fri_challenges(nullptr, C, I, pp.fri, alpha, fbetas, x_indices) != CP_OK) return verdict(6);
+  fill_record(I, alpha, fbetas.data(), x_indices.data(), rec);
+  return verdict(0);
+}
+
+size_t verify_threads(size_t n) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  size_t T = n / 4;  // at least four proofs per thread
+  if (T > 16) T = 16;
+  if (hw && T > hw) T = hw;
+  return T;
+}
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The passes of a batch. host(p, rec) is the host phase of proof p (any thread; it must not touch ctx or the HIP API): its
+// verdict, and with status 0 the challenge record. shared_cap: 2^cap_height x 4 words on the host, or null.
+template <class Host>
+int verify_batch_passes(cp_ctx *ctx, const friv::Instance &D, size_t proof_words, const uint64_t *shared_cap, const uint8_t *const *proofs,
+                        const size_t *lens, size_t n, size_t chunk, cp_verify_verdict *out, Host host) {
+  const size_t L = proof_words * 8, rec_w = friv::rec_words(D.n_batches, D.n_layers, D.n_queries), nq = D.n_queries;
+  if (chunk == 0) chunk = VERIFY_BATCH_PASS_BYTES / L ? VERIFY_BATCH_PASS_BYTES / L : 1;
+  if (chunk > n) chunk = n;
+  if (chunk > ((size_t)1 << 20)) chunk = (size_t)1 << 20;  // lanes of a pass are counted in 32 bits
+  const size_t cap_words = shared_cap ? (size_t)4 << D.cap_height : 0;
+  ArenaScope scope(ctx);  // drains the stream and recycles the staging area, whichever way the call ends
+  // page-locked staging of one pass: proofs | records | instance | shared cap | keys | active
+  const size_t o_rec = align256(chunk * L), o_inst = o_rec + align256(chunk * rec_w * 8), o_cap = o_inst + align256(sizeof(friv::Instance)),
+               o_keys = o_cap + align256(cap_words * 8), o_act = o_keys + align256(chunk * 4), st_bytes = o_act + align256(chunk);
+  char *st;
+  CP_TRY(pin_reserve(ctx, st_bytes, &st));
+  memcpy(st + o_inst, &D, sizeof D);
+  if (cap_words) memcpy(st + o_cap, shared_cap, cap_words * 8);
+  uint64_t *st_recs = (uint64_t *)(st + o_rec);
+  uint32_t *st_keys = (uint32_t *)(st + o_keys);
+  uint8_t *st_act = (uint8_t *)(st + o_act);
+  DevBag bag = ctx->bag();  // the device side, allocated by the first pass that has something to launch
+  char *d_proofs = nullptr, *d_recs = nullptr, *d_misc = nullptr;
+  const size_t m_cap = align256(sizeof(friv::Instance)), m_keys = m_cap + align256(cap_words * 8), m_act = m_keys + align256(chunk * 4),
+               m_bytes = m_act + align256(chunk);
+  for (size_t base = 0; base < n; base += chunk) {
+    const size_t m = n - base < chunk ? n - base : chunk;
+    host_phase(ctx, "verify_host");
+    hostu::parallel_for(m, verify_threads(m), [&](size_t i) {
+      out[base + i] = host(base + i, st_recs + i * rec_w);
+      st_act[i] = out[base + i].status == 0;
+    });
+    size_t n_active = 0;
+    for (size_t i = 0; i < m; i++) {
+      n_active += st_act[i];
+      if (st_act[i] && lens[base + i] != L) return set_error(ctx, CP_ERR_INTERNAL, "a parsed proof has %zu bytes, the shape's layout %zu", lens[base + i], L);
+    }
+    if (n_active == 0) continue;  // every verdict is the host's: nothing to launch
+    host_phase(ctx, "verify_upload");
+    hostu::parallel_for(m, verify_threads(m), [&](size_t i) {
+      if (st_act[i]) memcpy(st + i * L, proofs[base + i], L);  // also cures an unaligned caller pointer
+    });
+    if (!d_proofs) {
+      CP_TRY(alloc_status(ctx, bag.alloc(&d_proofs, chunk * L), chunk * L));
+      CP_TRY(alloc_status(ctx, bag.alloc(&d_recs, chunk * rec_w * 8), chunk * rec_w * 8));
+      CP_TRY(alloc_status(ctx, bag.alloc(&d_misc, m_bytes), m_bytes));
+      HIP_TRY(ctx, hipMemcpyAsync(d_misc, st + o_inst, sizeof(friv::Instance), hipMemcpyHostToDevice, ctx->stream));
+      if (cap_words) HIP_TRY(ctx, hipMemcpyAsync(d_misc + m_cap, st + o_cap, cap_words * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(d_proofs, st, m * L, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_recs, st_recs, m * rec_w * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_misc + m_act, st_act, m, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_misc + m_keys, 0xFF, m * 4, ctx->stream));
+    if (ctx->profiling) HIP_TRY(ctx, sync_stream(ctx));  // the upload is then inside the phase that names it
+    host_phase(ctx, "verify_device");
+    friv::KArgs a;
+    a.inst = (const friv::Instance *)d_misc;
+    a.proofs = (const uint64_t *)d_proofs;
+    a.recs = (const uint64_t *)d_recs;
+    a.shared_caps = cap_words ? (const uint64_t *)(d_misc + m_cap) : nullptr;
+    a.active = (const uint8_t *)(d_misc + m_act);
+    a.keys = (uint32_t *)(d_misc + m_keys);
+    a.proof_words = proof_words;
+    a.rec_words = (uint32_t)rec_w;
+    a.n_proofs = (uint32_t)m;
+    a.n_queries = (uint32_t)nq;
+    const unsigned blocks = blocks_for(m * nq, 64);
+    LAUNCH(ctx, "verify_paths", friv::k_paths, dim3(blocks, D.n_oracles + D.n_layers), dim3(64), a);
+    LAUNCH(ctx, "verify_arith", friv::k_arith, dim3(blocks), dim3(64), a);
+    HIP_TRY(ctx, hipMemcpyAsync(st_keys, d_misc + m_keys, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, sync_stream(ctx));
+    for (size_t i = 0; i < m; i++)
+      if (st_act[i]) out[base + i] = key_verdict(D, st_keys[i]);
+  }
+  host_phase(ctx, nullptr);
+  return CP_OK;
+}
+
+// the bounds cp_verify_fri_queries_with_challenges puts on a shape, with its words
+const char *hook_shape_problem(const cp_shape &sh) {
+  if (sh.degree_bits < 2 || sh.degree_bits + sh.rate_bits > 30 || sh.rate_bits < 0 || sh.num_challenges < 1 || sh.num_challenges > 8 ||
+      sh.n_arity < 0 || sh.n_arity > 8 || sh.cap_height < 0 || sh.cap_height > sh.degree_bits + sh.rate_bits || sh.num_query_rounds < 1 ||
+      sh.num_query_rounds > 255 || sh.num_wires < 1 || sh.num_constants < 0 || sh.num_routed_wires < 0 || sh.num_partial_products < 0 ||
+      sh.quotient_degree_factor < 1)
+    return "shape out of range";
+  for (int l = 0; l < sh.n_arity; l++)
+    if (sh.arity_bits[l] < 1 || sh.arity_bits[l] > 5) return "FRI arity out of range";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" int cp_verify_batch(cp_circuit *circ, const uint8_t *const *proofs, const size_t *proof_lens, size_t n_proofs, size_t chunk_proofs,
+                               cp_verify_verdict *verdicts_out) try {
+  if (!circ) return set_error(nullptr, CP_ERR_INVALID_ARG, "circuit is NULL");
+  cp_ctx *ctx = circ->ctx;
+  CHECK_CTX(ctx);
+  if (!proofs || !proof_lens || !verdicts_out) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL argument");
+  if (n_proofs == 0) return set_error(ctx, CP_ERR_INVALID_ARG, "no proofs");
+  if (!circ->has_gates) return set_error(ctx, CP_ERR_INVALID_ARG, "circuit has no gate set (cp_circuit_set_gates)");
+  for (size_t p = 0; p < n_proofs; p++)
+    if (!proofs[p] && proof_lens[p]) return set_error(ctx, CP_ERR_INVALID_ARG, "proof %zu is NULL", p);
+  const cp_shape &sh = circ->sh;
+  if (const char *why = hook_shape_problem(sh)) return set_error(ctx, CP_ERR_INVALID_ARG, "%s", why);
+  hostu::alloc_checkpoint();
+  friv::Instance D;
+  size_t proof_words;
+  CP_TRY(plonky2_layout(ctx, sh, true, D, proof_words));
+  std::vector<uint64_t> ks(sh.num_routed_wires);  // once per call, not once per proof
+  if (!ks.empty()) HIP_TRY(ctx, hipMemcpy(ks.data(), circ->k_is, ks.size() * 8, hipMemcpyDeviceToHost));
+  return verify_batch_passes(ctx, D, proof_words, circ->cs.cap_host.data(), proofs, proof_lens, n_proofs, chunk_proofs, verdicts_out,
+                             [&](size_t p, uint64_t *rec) { return verify_host_phase(*circ, ks.data(), proofs[p], proof_lens[p], rec); });
+} CP_CATCH(circ ? circ->ctx : nullptr)
+
+// Device twin of cp_verify_fri_queries_with_challenges: the query phase of n proofs of one shape with the challenges supplied
+// per proof, through the kernels cp_verify_batch launches.
+extern "C" int cp_verify_fri_queries_with_challenges_batch(cp_ctx *ctx, const cp_shape *shape, const uint64_t *cs_cap, const uint8_t *const *proofs,
+                                                           const size_t *proof_lens, size_t n_proofs, const uint64_t *alphas, const uint64_t *zetas,
+                                                           const uint64_t *fri_betas, const uint64_t *x_indices, size_t chunk_proofs,
+                                                           cp_verify_verdict *verdicts_out) try {
+  // the arguments first, the device last: what is wrong with a call is said without a GPU too
+  if (!shape || !proofs || !proof_lens || !alphas || !zetas || !x_indices || !verdicts_out || (shape->n_arity > 0 && !fri_betas))
+    return set_error(ctx, CP_ERR_INVALID_ARG, "NULL argument");
+  if (n_proofs == 0) return set_error(ctx, CP_ERR_INVALID_ARG, "no proofs");
+  const cp_shape &sh = *shape;
+  if (const char *why = hook_shape_problem(sh)) return set_error(ctx, CP_ERR_INVALID_ARG, "%s", why);
+  if (const char *why = shape_problem(sh)) return set_error(ctx, CP_ERR_INVALID_ARG, "%s", why);  // the kernels index by what the loader bounds
+  const size_t nl = (size_t)sh.n_arity, nq = (size_t)sh.num_query_rounds;
+  for (size_t p = 0; p < n_proofs; p++) {
+    if (!proofs[p] && proof_lens[p]) return set_error(ctx, CP_ERR_INVALID_ARG, "proof %zu is NULL", p);
+    bool canonical = alphas[2 * p] < gl::P && alphas[2 * p + 1] < gl::P && zetas[2 * p] < gl::P && zetas[2 * p + 1] < gl::P;
+    for (size_t l = 0; l < 2 * nl; l++) canonical = canonical && fri_betas[2 * nl * p + l] < gl::P;
+    if (!canonical) return set_error(ctx, CP_ERR_INVALID_ARG, "challenge is not canonical");
+  }
+  CHECK_CTX(ctx);
+  hostu::alloc_checkpoint();
+  friv::Instance D;
+  size_t proof_words;
+  CP_TRY(plonky2_layout(ctx, sh, cs_cap != nullptr, D, proof_words));
+  return verify_batch_passes(ctx, D, proof_words, cs_cap, proofs, proof_lens, n_proofs, chunk_proofs, verdicts_out, [&](size_t p, uint64_t *rec) {
+    ParsedProof pp;
+    if (parse_proof_bytes(nullptr, sh, nullptr, proofs[p], proof_lens[p], pp) != CP_OK) return parse_verdict();
+    const gl::Ext alpha{alphas[2 * p], alphas[2 * p + 1]}, zeta{zetas[2 * p], zetas[2 * p + 1]};
+    std::vector<gl::Ext> fb(nl);
+    for (size_t l = 0; l < nl; l++) fb[l] = gl::Ext{fri_betas[2 * (nl * p + l)], fri_betas[2 * (nl * p + l) + 1]};
+    FriVerifyInstance I;
+    plonky2_fri_instance(sh, &pp, zeta, I);
+    fill_record(I, alpha, fb.data(), x_indices + nq * p, rec);
+    return verdict(0);
+  });
+} CP_CATCH(ctx)

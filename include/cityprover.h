@@ -415,6 +415,40 @@ int cp_verify_fri_queries_with_challenges(const cp_shape *shape, const uint8_t *
                                           const uint64_t alpha[2], const uint64_t zeta[2], const uint64_t *fri_betas,
                                           const uint64_t *x_indices);
 
+/* ---- batches of proofs of ONE circuit: the query phase on the device ------------------------------------------------
+ * Proofs of one circuit share one shape, so they have the same length and every field at the same offset. cp_verify_batch
+ * runs, per proof, exactly what cp_verify runs before its query phase on host threads (shape-directed parse, transcript,
+ * vanishing identity at zeta, FRI challenges, proof of work), then uploads the accepted ones and checks every Merkle path
+ * and all the query arithmetic with two kernels (csrc/fri_verify.h): 96 % of a verification's permutations.
+ * One verdict per proof, the FIRST failure in cp_verify's own order; unused fields are -1:
+ *   status 0  accepted
+ *          1  malformed (any length prefix, truncation, trailing bytes, a length other than the shape's)
+ *          2  an element >= p
+ *          3  wrong number of public inputs
+ *          4  zeta in the subgroup, or an opening point on the LDE coset (`query` set in the second case)
+ *          5  vanishing identity (`detail` = challenge)
+ *          6  proof of work (a non-canonical witness included)
+ *          7  Merkle path of an oracle (`query`, `detail` = oracle)
+ *          8  FRI layer value (`query`, `detail` = layer)
+ *          9  Merkle path of a FRI layer (`query`, `detail` = layer)
+ *         10  final polynomial (`query`)
+ * Both functions return CP_OK whatever the verdicts are; CP_ERR_INVALID_ARG for NULL arguments, n_proofs == 0, a circuit
+ * without a gate set or a shape outside the bounds of cp_verify_fri_queries_with_challenges; CP_ERR_OOM for a refused
+ * allocation (the context stays usable). proofs[i] may be unaligned, and NULL where proof_lens[i] is 0.
+ * chunk_proofs: proofs per device pass; 0 = as many as 64 MiB of staged proof bytes hold (at least one). A call works
+ * through its proofs in passes of that size, so its memory is bounded whatever n_proofs is. */
+typedef struct cp_verify_verdict { int32_t status, query, detail, reserved; } cp_verify_verdict;
+int cp_verify_batch(cp_circuit *circuit, const uint8_t *const *proofs, const size_t *proof_lens, size_t n_proofs,
+                    size_t chunk_proofs, cp_verify_verdict *verdicts_out);
+/* The device twin of the audit hook above: the query phase of n_proofs proofs of one shape with the challenges supplied per
+ * proof (alphas: n x 2, zetas: n x 2, fri_betas: n x n_arity x 2, x_indices: n x num_query_rounds, reduced mod the LDE
+ * size). No circuit; cs_cap: the constants / sigmas cap (2^cap_height x 4), or NULL: oracle 0's paths are not checked. */
+int cp_verify_fri_queries_with_challenges_batch(cp_ctx *ctx, const cp_shape *shape, const uint64_t *cs_cap,
+                                                const uint8_t *const *proofs, const size_t *proof_lens, size_t n_proofs,
+                                                const uint64_t *alphas, const uint64_t *zetas, const uint64_t *fri_betas,
+                                                const uint64_t *x_indices, size_t chunk_proofs,
+                                                cp_verify_verdict *verdicts_out);
+
 /* ---- FRI primitives, the kernels the opening proof is built from ------------------------
  * cp_fri_combine_dev: comp[c] = sum_{j<k} alpha^j f_j[c] over F_p^2 for k base-field vectors of length n (polynomial j at
  *   polys_dev + j*n) — plonky2's `ReducingFactor::reduce_polys_base`, the batch polynomial of the FRI opening proof.

@@ -195,6 +195,23 @@ impl Circuit {
         Err(anyhow!("cityprover[{rc}]: {}", last_error(ptr::null_mut())))
     }
 
+    /// `CircuitData::verify` on many proofs of this circuit at once (`cp_verify_batch`): the query phase runs on the
+    /// device. One verdict per proof (`status` 0 = accepted; the table is in include/cityprover.h); `Err` only for a call
+    /// that could not run. `chunk_proofs` 0 = the library's default pass size.
+    pub fn verify_batch(&self, proofs: &[&[u8]], chunk_proofs: usize) -> Result<Vec<ffi::CpVerifyVerdict>> {
+        if proofs.is_empty() {
+            return Ok(Vec::new());
+        }
+        let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut out = vec![ffi::CpVerifyVerdict { status: -1, query: -1, detail: -1, reserved: 0 }; proofs.len()];
+        let rc = unsafe { ffi::cp_verify_batch(self.raw, ptrs.as_ptr(), lens.as_ptr(), proofs.len(), chunk_proofs, out.as_mut_ptr()) };
+        if rc != ffi::CP_OK {
+            bail!("cp_verify_batch[{rc}]: {}", last_error(ptr::null_mut()));
+        }
+        Ok(out)
+    }
+
     pub fn raw(&self) -> *mut ffi::CpCircuit {
         self.raw
     }
