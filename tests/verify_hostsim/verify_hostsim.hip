@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstring>
+#include <thread>
+#include <vector>
 
 #include "../../city-rollup_amd/csrc/poseidon_tables.h"
 #include "../../city-rollup_amd/csrc/fri_verify.h"
@@ -27,6 +29,18 @@ uint32_t vh_query_phase(const friv::Instance *inst, const uint64_t *proof_words,
     if (k < key) key = k;
   }
   return key;
+}
+// vh_query_phase over n (proof, record) pairs laid out as the kernels get them: [proof][proof_words], [proof][rec_words]
+void vh_query_phase_many(const friv::Instance *inst, const uint64_t *proofs, size_t proof_words, const uint64_t *recs, size_t rec_words,
+                         const uint64_t *shared_caps, size_t n, uint32_t *keys_out) {
+  unsigned T = std::thread::hardware_concurrency();
+  T = T < 1 ? 1 : T > 8 ? 8 : T;
+  std::vector<std::thread> pool;
+  for (unsigned t = 0; t < T; t++)
+    pool.emplace_back([=] {
+      for (size_t p = t; p < n; p += T) keys_out[p] = vh_query_phase(inst, proofs + p * proof_words, recs + p * rec_words, shared_caps);
+    });
+  for (std::thread &th : pool) th.join();
 }
 // compute_evaluation alone: evals = 2^ab extension values in the proof's (bit-reversed) order
 void vh_coset_eval(const uint64_t *evals, uint64_t x, uint32_t within, uint32_t ab, uint64_t g, const uint64_t *beta, uint64_t *out) {
