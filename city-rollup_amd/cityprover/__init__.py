@@ -1613,8 +1613,12 @@ ABI.update({
     "cp_stark_prove_batch": (ctypes.c_int, [_vp, ctypes.POINTER(StarkDesc), ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.c_int, _u64p, _u64p,
                                             ctypes.POINTER(ChallengerState), ctypes.POINTER(ctypes.c_int), _u64p, _u8pp, ctypes.POINTER(ctypes.c_size_t)]),
     "cp_stark_verify": (ctypes.c_int, [ctypes.POINTER(StarkDesc), _u64p, _u64p, ctypes.POINTER(ChallengerState), ctypes.c_char_p, ctypes.c_size_t]),
+    "cp_stark_verify_batch": (ctypes.c_int, [_vp, ctypes.POINTER(StarkDesc), ctypes.c_size_t, _u64p, _u64p, ctypes.POINTER(ChallengerState),
+                                             ctypes.POINTER(ctypes.c_char_p), _szp, ctypes.c_size_t, ctypes.c_uint, _vp]),
 })
 STARK_BATCH_MAX = 64
+# path_form of cp_stark_verify_batch: which kernel checks the Merkle paths
+PATHS_AUTO, PATHS_LANE, PATHS_COOP = 0, 1, 2
 
 
 def _opt_u64(x):
@@ -1786,3 +1790,22 @@ def stark_verify(desc, challenger, proof, publics=None, globals_=None):
     rc = lib.cp_stark_verify(ctypes.byref(desc), pp, gp, ctypes.byref(challenger), proof, len(proof))
     if rc != 0:
         raise CityProverError(f"[{rc}] " + lib.cp_last_error(None).decode())
+
+
+def stark_verify_batch(prover, desc, challengers, proofs, publics=None, globals_=None, chunk=0, path_form=PATHS_AUTO):
+    """cp_stark_verify_batch: B proofs of ONE description -> list of B (status, query, detail), the statuses of VERDICT. publics /
+    globals_: (B, n_public) / (B, n_global) or None. The ChallengerState of every ACCEPTED proof is advanced in place as stark_verify
+    advances it; a rejected proof's stays as it came in. Raises only for a call that could not run (then nothing has moved)."""
+    keep, ptrs, lens = _proof_array(proofs)
+    B = len(keep)
+    if len(challengers) != B:
+        raise ValueError("one challenger per proof")
+    (pp, gp), keep2 = zip(*[_opt_u64(x) for x in (publics, globals_)])
+    ch = (ChallengerState * max(B, 1))()
+    for i, c in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(ch[i]), ctypes.byref(c), ctypes.sizeof(ChallengerState))
+    out = np.zeros(max(B, 1), VERDICT)
+    prover._check(prover.lib.cp_stark_verify_batch(prover.ctx, ctypes.byref(desc), B, pp, gp, ch, ptrs, lens, int(chunk), int(path_form), out.ctypes.data))
+    for i, c in enumerate(challengers):
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(ch[i]), ctypes.sizeof(ChallengerState))
+    return [(int(v["status"]), int(v["query"]), int(v["detail"])) for v in out[:B]]

@@ -1,14 +1,18 @@
 // The query phase of plonky2 `verify_fri_proof` over proofs of ONE shape, one definition for the host and the device: what
 // verify.inc's verify_fri_queries does for one proof on one core, per (proof, query round, tree) and per (proof, query round).
-// cp_verify_batch and cp_verify_fri_queries_with_challenges_batch (verify.inc) launch the two kernels below; tests/verify_hostsim
-// compiles check_path / check_query for the host. Nothing here knows plonky2's four oracles: the instance table says how many
-// oracles there are, how long their leaves are and where every field of a query round lies.
+// cp_verify_batch and cp_verify_fri_queries_with_challenges_batch (verify.inc) launch k_paths and k_arith below, cp_stark_verify_batch
+// (stark.inc) k_arith and either k_paths or its twelve-lane form k_paths_coop; tests/verify_hostsim compiles check_path / check_query
+// for the host. Nothing here knows plonky2's four oracles or a STARK's two or three: the instance table says how many oracles there
+// are, how long their leaves are and where every field of a query round lies.
 //
 // Proofs of one shape have the same length and every field at the same offset (the shape dictates every length prefix:
 // parse_fri_proof, parse_proof_bytes), so a batch is an array [proof][words] with one stride, read where the prover's bytes lie.
 #pragma once
 #include "gl.h"
 #include "poseidon.h"
+#if defined(__HIPCC__)
+#include "poseidon_coop.h"
+#endif
 
 namespace friv {
 
@@ -231,6 +235,82 @@ __global__ __launch_bounds__(64) void k_paths(KArgs a) {
   if (!a.active[p]) return;
   const uint32_t key = path_key((InstancePtr)a.inst, a.proofs + p * a.proof_words, a.recs + (size_t)p * a.rec_words, a.shared_caps, qi, blockIdx.y);
   if (key != KEY_NONE) atomicMin(a.keys + p, key);
+}
+
+// check_path / path_key with TWELVE lanes per path (poseidon_coop.h), for batches of few proofs with long leaves: three STARK proofs
+// of 84 query rounds are 252 paths per tree - with k_paths four waves, each alone on its SIMD with a chain of up to 114
+// permutations. Here a group of twelve lanes holds one sponge state, one element per lane; five paths per wave, lanes 60..63 idle.
+// grid (ceil(n_proofs n_queries / 20), n_oracles + n_layers), four waves per workgroup. blockIdx.y names the tree, so leaf
+// length, depth and with them every trip count are uniform over the workgroup: all 64 lanes of a wave make every pcoop::permute
+// call together, groups past the end or of an inactive proof with dummies (they load nothing and report nothing).
+__global__ __launch_bounds__(256) void k_paths_coop(KArgs a) {
+  using namespace pcoop;
+  __shared__ __attribute__((aligned(16))) uint64_t sh[WAVES][STATES_PER_WAVE * GROUP];
+  const InstancePtr I = (InstancePtr)a.inst;
+  const uint32_t tree = blockIdx.y, n_or = I->n_oracles;
+  // the tree's own numbers (path_key), all wave-uniform
+  uint32_t leaf_off, leaf_len, sib_off, depth, cap_off, ord, shift = 0;
+  bool shared = false;
+  if (tree < n_or) {
+    const uint32_t src = I->cap_src[tree];
+    if (src == 0) return;  // the whole workgroup: this oracle's paths are not checked
+    shared = src == 2;
+    leaf_off = I->leaf_off[tree]; leaf_len = I->leaf_len[tree]; sib_off = I->sib_off[tree]; depth = I->depth0; cap_off = I->cap_off[tree];
+    ord = ord_oracle(tree);
+  } else {
+    const uint32_t l = tree - n_or;
+    for (uint32_t k = 0; k <= l; k++) shift += I->arity_bits[k];
+    leaf_off = I->ev_off[l]; leaf_len = 2u << I->arity_bits[l]; sib_off = I->path_off[l]; depth = I->layer_depth[l]; cap_off = I->fcap_off[l];
+    ord = ord_layer_path(n_or, l);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool lane_used = lane < STATES_PER_WAVE * GROUP;
+  const int g = lane_used ? lane / GROUP : 0, e = lane_used ? lane - g * GROUP : 0;  // lanes 60..63 shadow group 0 / element 0
+  const size_t t = (size_t)blockIdx.x * STATES_PER_BLOCK + wave * STATES_PER_WAVE + g;
+  bool active = lane_used && t < (size_t)a.n_proofs * a.n_queries;
+  const uint32_t p = active ? (uint32_t)(t / a.n_queries) : 0, qi = active ? (uint32_t)(t % a.n_queries) : 0;
+  active = active && a.active[p];
+  const uint64_t *pw = a.proofs + p * a.proof_words;
+  const uint64_t *round = pw + I->q_base + (size_t)qi * I->q_words;
+  const uint64_t *leaf = round + leaf_off, *sib = round + sib_off;
+  const uint64_t index = active ? a.recs[(size_t)p * a.rec_words + rec_index(I->n_batches, I->n_layers, qi)] >> shift : 0;
+  uint32_t coef[GROUP];
+#pragma unroll
+  for (int k = 0; k < GROUP; k++) coef[k] = mds_coef(e, k);
+  // hash_or_noop of the leaf: the overwrite sponge, which is check_path's case analysis with whole permutations - a full chunk
+  // overwrites the eight rate lanes and keeps the capacity, a partial last chunk keeps what it does not cover (so the chunk before
+  // it keeps everything), a leaf of 5 .. 7 elements is one partial chunk over the zero state
+  uint64_t x = 0;
+  if (leaf_len <= 4) {  // a leaf of at most four elements is its own digest
+    if (active && (uint32_t)e < leaf_len) x = leaf[e];
+  } else {
+    uint64_t nxt = (active && e < RATE_ && (uint32_t)e < leaf_len) ? leaf[e] : 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < leaf_len; j += RATE_) {
+      if (e < RATE_ && j + e < leaf_len) x = nxt;
+      const uint32_t n0 = j + RATE_;
+      nxt = (active && e < RATE_ && n0 + e < leaf_len) ? leaf[n0 + e] : 0;  // fetched under the permutation
+      x = permute(x, g, e, lane_used, sh[wave], coef);
+    }
+  }
+  // the climb: the digest sits in lanes 0..3 of the group; it stays there or moves to lanes 4..7 by the index bit, the sibling takes
+  // the other half, lanes 8..11 carry the zero capacity
+#pragma unroll 1
+  for (uint32_t i = 0; i < depth; i++) {
+    const bool right = (index >> i) & 1;
+    const uint64_t below = __shfl(x, (lane + 60) & 63);  // lane e of a group sees lane e - 4: the digest, for e = 4..7
+    const uint64_t s = (active && e < 8) ? sib[4 * i + (e & 3)] : 0;
+    x = e < 4 ? (right ? s : x) : e < 8 ? (right ? below : s) : 0;
+    x = permute(x, g, e, lane_used, sh[wave], coef);
+  }
+  const uint64_t top = index >> depth;  // depth <= 30
+  bool bad = false;
+  if (active && e < 4) {
+    bad = top >= ((uint64_t)1 << I->cap_height);  // an index past the cap
+    if (!bad) bad = x != ((shared ? a.shared_caps : pw) + cap_off)[4 * top + e];
+  }
+  const uint64_t failed = __ballot(bad);
+  if (active && e == 0 && ((failed >> (g * GROUP)) & 0xF)) atomicMin(a.keys + p, qi << 8 | ord);
 }
 
 // grid (ceil(n_proofs n_queries / 64)), one lane per (proof, query round)

@@ -543,6 +543,218 @@ int stark_prove_batch_impl(cp_ctx *ctx, const cp_stark_desc *desc, const StarkSh
   return CP_OK;
 }
 
+// ---- the verifier's two halves: everything before `verify_fri_proof` (cp_stark_verify, and per proof cp_stark_verify_batch) ----
+struct StarkFront {
+  std::vector<uint64_t> caps[3], lq, nxt;  // the caps; the openings as the transcript takes them: local | quotient, next
+  gl::Ext zeta;
+  cp_challenger_state ch;  // after the openings
+  size_t o = 0;            // where the FriProof starts
+  int status = 0, detail = -1;  // the class of a refusal in cp_verify_verdict's terms
+};
+// Parse of everything before the FriProof, transcript, round challenges, alphas, zeta, the constraints at zeta against the
+// quotient, the openings into the transcript. desc, publics, globals and `in` are validated by the caller. Errors go to the
+// thread's own message, with cp_stark_verify's words.
+int stark_verify_front(const cp_stark_desc *desc, const StarkShape &s, const uint64_t *publics, const uint64_t *globals, const cp_challenger_state &in,
+                       const uint8_t *proof, size_t proof_len, StarkFront &f) {
+  const size_t n_tr = s.k1 ? 2 : 1, cap_w = (size_t)4 << s.ch;
+  // ---- parse ----
+  size_t o = 0;
+  bool bad = false, noncanonical = false;
+  auto u64 = [&]() -> uint64_t {
+    if (proof_len - o < 8) { bad = true; return 0; }
+    uint64_t v;
+    memcpy(&v, proof + o, 8);
+    o += 8;
+    return v;
+  };
+  auto words = [&](size_t cnt, std::vector<uint64_t> &out) {
+    if (bad || cnt > (proof_len - o) / 8) { bad = true; return; }
+    out.resize(cnt);
+    memcpy(out.data(), proof + o, cnt * 8);
+    o += cnt * 8;
+    if (!all_canonical(out.data(), cnt)) noncanonical = true;
+  };
+  std::vector<uint64_t> loc, qz;
+  std::vector<uint64_t> *caps = f.caps, &nxt = f.nxt;
+  if (u64() != n_tr) bad = true;
+  for (size_t i = 0; i < n_tr + 1 && !bad; i++) {
+    if (u64() != ((uint64_t)1 << s.ch)) bad = true;
+    words(cap_w, caps[i]);
+  }
+  if (!bad && u64() != s.kt) bad = true;
+  words(2 * s.kt, loc);
+  if (!bad && u64() != s.kt) bad = true;
+  words(2 * s.kt, nxt);
+  if (!bad && u64() != s.kq) bad = true;
+  words(2 * s.kq, qz);
+  f.status = 1;
+  if (bad) return set_error(nullptr, CP_ERR_VERIFY, "malformed STARK proof");
+  f.status = 2;
+  if (noncanonical) return set_error(nullptr, CP_ERR_VERIFY, "a field element of the proof is not canonical (>= p)");
+  hostu::alloc_checkpoint();
+  // ---- transcript ----
+  cp_challenger_state &ch = f.ch;
+  ch = in;
+  CP_TRY(cp_challenger_observe(&ch, caps[0].data(), cap_w));
+  std::vector<uint64_t> rch(2 * (size_t)desc->n_round_challenges, 0);
+  if (s.k1) {
+    for (uint32_t i = 0; i < desc->n_round_challenges; i++) CP_TRY(cp_challenger_challenges(&ch, &rch[2 * i], 1));
+    CP_TRY(cp_challenger_observe(&ch, caps[1].data(), cap_w));
+  }
+  uint64_t alphas[air::MAX_ALPHAS];
+  CP_TRY(cp_challenger_challenges(&ch, alphas, s.na));
+  CP_TRY(cp_challenger_observe(&ch, caps[n_tr].data(), cap_w));
+  uint64_t zw[2];
+  CP_TRY(cp_challenger_challenges(&ch, zw, 2));
+  const gl::Ext zeta{zw[0], zw[1]};
+  f.zeta = zeta;
+  // ---- the constraints at zeta against Z_H(zeta) * sum_i zeta^(n i) t_i(zeta) ----
+  const air::Program &P = desc->constraints->P;
+  std::vector<gl::Ext> pe(desc->n_public), ge(desc->n_global), vals;
+  for (uint32_t i = 0; i < desc->n_public; i++) pe[i] = gl::Ext{publics[i], 0};
+  for (uint32_t i = 0; i < desc->n_global; i++) ge[i] = gl::Ext{globals[i], 0};
+  air_eval_ext_row(P, (const gl::Ext *)loc.data(), (const gl::Ext *)nxt.data(), pe.data(), ge.data(), (const gl::Ext *)rch.data(), vals);
+  const ZetaSelectors zs = zeta_selectors(zeta, s.db);
+  f.status = 4;
+  if (zs.zh.a == 0 && zs.zh.b == 0) return set_error(nullptr, CP_ERR_VERIFY, "zeta lies in the trace domain");
+  f.status = 5;
+  for (uint32_t a = 0; a < s.na; a++) {
+    gl::Ext acc{0, 0};
+    for (uint32_t r : P.roots) {
+      gl::Ext v = vals[P.ops[r].a];
+      if (P.ops[r].op == air::R_ASSERT_TRANSITION) v = gl::ext_mul(v, zs.z_last);
+      else if (P.ops[r].op == air::R_ASSERT_FIRST) v = gl::ext_mul(v, zs.l_first);
+      else if (P.ops[r].op == air::R_ASSERT_LAST) v = gl::ext_mul(v, zs.l_last);
+      acc = gl::ext_add(gl::ext_scale(acc, alphas[a]), v);
+    }
+    gl::Ext t{0, 0};
+    for (size_t k = (size_t)1 << s.q; k-- > 0;) t = gl::ext_add(gl::ext_mul(t, zs.zn), gl::Ext{qz[2 * (((size_t)a << s.q) + k)], qz[2 * (((size_t)a << s.q) + k) + 1]});
+    const gl::Ext lhs = gl::ext_mul(t, zs.zh);
+    f.detail = (int)a;
+    if (lhs.a != acc.a || lhs.b != acc.b) return set_error(nullptr, CP_ERR_VERIFY, "the constraints do not vanish: quotient identity fails at zeta for challenge %u", a);
+  }
+  f.status = 0;
+  f.detail = -1;
+  // ---- the openings into the transcript ----
+  f.lq = loc;
+  f.lq.insert(f.lq.end(), qz.begin(), qz.end());
+  CP_TRY(cp_challenger_observe(&ch, f.lq.data(), f.lq.size()));
+  CP_TRY(cp_challenger_observe(&ch, nxt.data(), nxt.size()));
+  f.o = o;
+  return CP_OK;
+}
+
+// The FRI instance of a STARK proof in cp_fri_verify's terms: 2 or 3 oracles (trace, [extended,] quotient), everything at zeta,
+// the trace rounds at g zeta. Points, caps and opened values are the front's; without one the table alone (points 0).
+struct StarkFriInstance {
+  size_t n_or;
+  cp_fri_oracle_info infos[3];
+  const uint64_t *cap_ptrs[3] = {nullptr, nullptr, nullptr};
+  cp_fri_poly_range r0[3], r1[2];
+  cp_fri_batch fb[2];
+  const uint64_t *opened[2] = {nullptr, nullptr};
+  StarkFriInstance(const StarkFriInstance &) = delete;  // fb points into r0 / r1
+  StarkFriInstance(const StarkShape &s, const StarkFront *f) {
+    const gl::Ext zeta = f ? f->zeta : gl::Ext{0, 0};
+    if (f) {
+      for (int i = 0; i < 3; i++) cap_ptrs[i] = f->caps[i].data();
+      opened[0] = f->lq.data();
+      opened[1] = f->nxt.data();
+    }
+    uint64_t g = gl::pow(7, (gl::P - 1) >> 32);
+    for (int i = s.db; i < 32; i++) g = gl::sqr(g);
+    const size_t n_tr = s.k1 ? 2 : 1;
+    n_or = n_tr + 1;
+    const uint32_t qi = (uint32_t)n_tr;
+    infos[0] = {(uint32_t)s.k0, 0}; infos[1] = {(uint32_t)(s.k1 ? s.k1 : s.kq), 0}; infos[2] = {(uint32_t)s.kq, 0};
+    r0[0] = {0, 0, (uint32_t)s.k0}; r0[1] = {1, 0, (uint32_t)s.k1}; r0[2] = {qi, 0, (uint32_t)s.kq};
+    r1[0] = {0, 0, (uint32_t)s.k0}; r1[1] = {1, 0, (uint32_t)s.k1};
+    if (!s.k1) r0[1] = r0[2];
+    fb[0] = {{zeta.a, zeta.b}, r0, s.k1 ? (size_t)3 : (size_t)2};
+    fb[1] = {{gl::mul(zeta.a, g), gl::mul(zeta.b, g)}, r1, s.k1 ? (size_t)2 : (size_t)1};
+  }
+};
+
+// the same instance as verify.inc's structures (what cp_fri_verify builds from its arguments); f == nullptr: no caps, points, values
+void stark_fri_instance(const cp_stark_desc *desc, const StarkShape &s, const StarkFront *f, FriVerifyInstance &I) {
+  const StarkFriInstance fi(s, f);
+  load_fri_cfg(nullptr, &desc->fri, I.cfg);  // stark_shape accepted it
+  I.db = s.db;
+  I.n_oracles = (int)fi.n_or;
+  for (size_t o = 0; o < fi.n_or; o++) {
+    I.kk[o] = I.leaf_len[o] = fi.infos[o].num_polys;
+    I.caps[o] = fi.cap_ptrs[o];
+  }
+  I.points.resize(2);
+  I.ranges.assign(2, {});
+  I.opened.assign(2, {});
+  for (size_t b = 0; b < 2; b++) {
+    I.points[b] = gl::Ext{fi.fb[b].point[0], fi.fb[b].point[1]};
+    size_t cnt = 0;
+    for (size_t r = 0; r < fi.fb[b].n_ranges; r++) {
+      I.ranges[b].push_back(fi.fb[b].ranges[r]);
+      cnt += fi.fb[b].ranges[r].count;
+    }
+    if (!f) continue;
+    I.opened[b].resize(cnt);
+    for (size_t j = 0; j < cnt; j++) I.opened[b][j] = gl::Ext{fi.opened[b][2 * j], fi.opened[b][2 * j + 1]};
+  }
+}
+
+// The STARK proof format as the kernels of fri_verify.h read it: trace_caps | quotient_cap | local | next | quotient openings |
+// FriProof, every oracle's cap in the proof itself. Refuses what the instance table cannot hold.
+int stark_layout(cp_ctx *ctx, const cp_stark_desc *desc, const StarkShape &s, FriVerifyInstance &I, friv::Instance &D, size_t &proof_words) {
+  if (desc->fri.num_query_rounds > 255) return set_error(ctx, CP_ERR_INVALID_ARG, "more than 255 query rounds");  // the failure key: query << 8 | ordinal
+  if (s.kq < 1 || s.kq > 65535) return set_error(ctx, CP_ERR_INVALID_ARG, "quotient width out of range");
+  stark_fri_instance(desc, s, nullptr, I);
+  if (I.n_oracles > friv::MAX_ORACLES || I.cfg.n_arity > friv::MAX_LAYERS) return set_error(ctx, CP_ERR_INVALID_ARG, "too many oracles / FRI layers");
+  memset(&D, 0, sizeof D);
+  const size_t cap_n = (size_t)1 << s.ch;
+  size_t o = 1;
+  for (int b = 0; b < I.n_oracles; b++) { o += 1; D.cap_src[b] = 1; D.cap_off[b] = (uint32_t)o; o += cap_n * 4; }
+  o += 3 + 4 * s.kt + 2 * s.kq;
+  proof_words = friv_layout(I, o, D);
+  D.n_batches = 2;
+  uint32_t nr = 0;
+  for (size_t b = 0; b < 2; b++) {
+    D.batch_first[b] = nr;
+    for (const cp_fri_poly_range &R : I.ranges[b]) {
+      if (nr >= (uint32_t)friv::MAX_RANGES) return set_error(ctx, CP_ERR_INVALID_ARG, "too many opening ranges");
+      D.r_oracle[nr] = R.oracle; D.r_first[nr] = R.first; D.r_count[nr] = R.count;
+      nr++;
+    }
+  }
+  D.batch_first[2] = nr;
+  D.n_ranges = nr;
+  if (proof_words > ((size_t)1 << 31)) return set_error(ctx, CP_ERR_INVALID_ARG, "description out of range: a proof of more than 2^31 words");
+  return CP_OK;
+}
+
+// Everything cp_stark_verify does before its query phase, for one proof of a batch, on whatever thread: the front above, then what
+// cp_fri_verify does before verify_fri_queries (shape-directed parse of the FriProof, FRI challenges, proof of work) - the same
+// functions in the same order. Status 0: `rec` holds the challenge record, ch_out the challenger as cp_stark_verify leaves it.
+cp_verify_verdict stark_verify_host_phase(const cp_stark_desc *desc, const StarkShape &s, const uint64_t *publics,
+                                          const uint64_t *globals, const cp_challenger_state &ch_in, const uint8_t *proof, size_t len,
+                                          cp_challenger_state &ch_out, uint64_t *rec) {
+  StarkFront f;
+  if (stark_verify_front(desc, s, publics, globals, ch_in, proof, len, f) != CP_OK) return verdict(f.status, -1, f.detail);
+  FriVerifyInstance I;
+  stark_fri_instance(desc, s, &f, I);
+  Rd r{proof + f.o, len - f.o};
+  ParsedFri pf;
+  if (parse_fri_proof(nullptr, I, r, pf) != CP_OK || r.o != len - f.o) return verdict(1);
+  if (r.noncanonical) return verdict(2);
+  HostChallenger C;
+  challenger_load(C, f.ch);
+  gl::Ext alpha;
+  std::vector<gl::Ext> fbetas;
+  std::vector<uint64_t> x_indices;
+  if (fri_challenges(nullptr, C, I, pf, alpha, fbetas, x_indices) != CP_OK) return verdict(6);
+  fill_record(I, alpha, fbetas.data(), x_indices.data(), rec);
+  challenger_store(C, ch_out);
+  return verdict(0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -872,93 +1084,50 @@ int cp_stark_verify(const cp_stark_desc *desc, const uint64_t *publics, const ui
   if ((desc->n_public && !publics) || (desc->n_global && !globals)) return set_error(nullptr, CP_ERR_INVALID_ARG, "NULL publics / globals");
   if (!all_canonical(publics, desc->n_public) || !all_canonical(globals, desc->n_global)) return set_error(nullptr, CP_ERR_INVALID_ARG, "a public input / global value is not canonical");
   if (const char *why = challenger_problem(challenger)) return set_error(nullptr, CP_ERR_INVALID_ARG, "%s", why);
-  const size_t n_tr = s.k1 ? 2 : 1, cap_w = (size_t)4 << s.ch;
-  // ---- parse ----
-  size_t o = 0;
-  bool bad = false, noncanonical = false;
-  auto u64 = [&]() -> uint64_t {
-    if (proof_len - o < 8) { bad = true; return 0; }
-    uint64_t v;
-    memcpy(&v, proof + o, 8);
-    o += 8;
-    return v;
-  };
-  auto words = [&](size_t cnt, std::vector<uint64_t> &out) {
-    if (bad || cnt > (proof_len - o) / 8) { bad = true; return; }
-    out.resize(cnt);
-    memcpy(out.data(), proof + o, cnt * 8);
-    o += cnt * 8;
-    if (!all_canonical(out.data(), cnt)) noncanonical = true;
-  };
-  std::vector<uint64_t> caps[3], loc, nxt, qz;
-  if (u64() != n_tr) bad = true;
-  for (size_t i = 0; i < n_tr + 1 && !bad; i++) {
-    if (u64() != ((uint64_t)1 << s.ch)) bad = true;
-    words(cap_w, caps[i]);
-  }
-  if (!bad && u64() != s.kt) bad = true;
-  words(2 * s.kt, loc);
-  if (!bad && u64() != s.kt) bad = true;
-  words(2 * s.kt, nxt);
-  if (!bad && u64() != s.kq) bad = true;
-  words(2 * s.kq, qz);
-  if (bad) return set_error(nullptr, CP_ERR_VERIFY, "malformed STARK proof");
-  if (noncanonical) return set_error(nullptr, CP_ERR_VERIFY, "a field element of the proof is not canonical (>= p)");
-  hostu::alloc_checkpoint();
-  // ---- transcript ----
-  cp_challenger_state ch = *challenger;
-  CP_TRY(cp_challenger_observe(&ch, caps[0].data(), cap_w));
-  std::vector<uint64_t> rch(2 * (size_t)desc->n_round_challenges, 0);
-  if (s.k1) {
-    for (uint32_t i = 0; i < desc->n_round_challenges; i++) CP_TRY(cp_challenger_challenges(&ch, &rch[2 * i], 1));
-    CP_TRY(cp_challenger_observe(&ch, caps[1].data(), cap_w));
-  }
-  uint64_t alphas[air::MAX_ALPHAS];
-  CP_TRY(cp_challenger_challenges(&ch, alphas, s.na));
-  CP_TRY(cp_challenger_observe(&ch, caps[n_tr].data(), cap_w));
-  uint64_t zw[2];
-  CP_TRY(cp_challenger_challenges(&ch, zw, 2));
-  const gl::Ext zeta{zw[0], zw[1]};
-  // ---- the constraints at zeta against Z_H(zeta) * sum_i zeta^(n i) t_i(zeta) ----
-  const air::Program &P = desc->constraints->P;
-  std::vector<gl::Ext> pe(desc->n_public), ge(desc->n_global), vals;
-  for (uint32_t i = 0; i < desc->n_public; i++) pe[i] = gl::Ext{publics[i], 0};
-  for (uint32_t i = 0; i < desc->n_global; i++) ge[i] = gl::Ext{globals[i], 0};
-  air_eval_ext_row(P, (const gl::Ext *)loc.data(), (const gl::Ext *)nxt.data(), pe.data(), ge.data(), (const gl::Ext *)rch.data(), vals);
-  const ZetaSelectors zs = zeta_selectors(zeta, s.db);
-  if (zs.zh.a == 0 && zs.zh.b == 0) return set_error(nullptr, CP_ERR_VERIFY, "zeta lies in the trace domain");
-  for (uint32_t a = 0; a < s.na; a++) {
-    gl::Ext acc{0, 0};
-    for (uint32_t r : P.roots) {
-      gl::Ext v = vals[P.ops[r].a];
-      if (P.ops[r].op == air::R_ASSERT_TRANSITION) v = gl::ext_mul(v, zs.z_last);
-      else if (P.ops[r].op == air::R_ASSERT_FIRST) v = gl::ext_mul(v, zs.l_first);
-      else if (P.ops[r].op == air::R_ASSERT_LAST) v = gl::ext_mul(v, zs.l_last);
-      acc = gl::ext_add(gl::ext_scale(acc, alphas[a]), v);
-    }
-    gl::Ext t{0, 0};
-    for (size_t k = (size_t)1 << s.q; k-- > 0;) t = gl::ext_add(gl::ext_mul(t, zs.zn), gl::Ext{qz[2 * (((size_t)a << s.q) + k)], qz[2 * (((size_t)a << s.q) + k) + 1]});
-    const gl::Ext lhs = gl::ext_mul(t, zs.zh);
-    if (lhs.a != acc.a || lhs.b != acc.b) return set_error(nullptr, CP_ERR_VERIFY, "the constraints do not vanish: quotient identity fails at zeta for challenge %u", a);
-  }
-  // ---- openings into the transcript, then verify_fri_proof ----
-  std::vector<uint64_t> lq(loc);
-  lq.insert(lq.end(), qz.begin(), qz.end());
-  CP_TRY(cp_challenger_observe(&ch, lq.data(), lq.size()));
-  CP_TRY(cp_challenger_observe(&ch, nxt.data(), nxt.size()));
-  uint64_t g = gl::pow(7, (gl::P - 1) >> 32);
-  for (int i = s.db; i < 32; i++) g = gl::sqr(g);
-  const size_t n_or = n_tr + 1;
-  const uint32_t qi = (uint32_t)n_tr;
-  cp_fri_oracle_info infos[3] = {{(uint32_t)s.k0, 0}, {(uint32_t)(s.k1 ? s.k1 : s.kq), 0}, {(uint32_t)s.kq, 0}};
-  const uint64_t *cap_ptrs[3] = {caps[0].data(), caps[1].data(), caps[2].data()};
-  cp_fri_poly_range r0[3] = {{0, 0, (uint32_t)s.k0}, {1, 0, (uint32_t)s.k1}, {qi, 0, (uint32_t)s.kq}}, r1[2] = {{0, 0, (uint32_t)s.k0}, {1, 0, (uint32_t)s.k1}};
-  if (!s.k1) r0[1] = r0[2];
-  cp_fri_batch fb[2] = {{{zeta.a, zeta.b}, r0, s.k1 ? (size_t)3 : (size_t)2}, {{gl::mul(zeta.a, g), gl::mul(zeta.b, g)}, r1, s.k1 ? (size_t)2 : (size_t)1}};
-  const uint64_t *opened[2] = {lq.data(), nxt.data()};
-  CP_TRY(cp_fri_verify(&desc->fri, infos, n_or, cap_ptrs, fb, 2, opened, &ch, proof + o, proof_len - o));
-  *challenger = ch;
+  StarkFront f;
+  CP_TRY(stark_verify_front(desc, s, publics, globals, *challenger, proof, proof_len, f));
+  StarkFriInstance fi(s, &f);
+  CP_TRY(cp_fri_verify(&desc->fri, fi.infos, fi.n_or, fi.cap_ptrs, fi.fb, 2, fi.opened, &f.ch, proof + f.o, proof_len - f.o));
+  *challenger = f.ch;
   return CP_OK;
 } CP_CATCH(nullptr)
+
+int cp_stark_verify_batch(cp_ctx *ctx, const cp_stark_desc *desc, size_t n_proofs, const uint64_t *publics, const uint64_t *globals,
+                          cp_challenger_state *challengers, const uint8_t *const *proofs, const size_t *proof_lens, size_t chunk_proofs,
+                          unsigned path_form, cp_verify_verdict *verdicts_out) try {
+  // the arguments first, the context last, and nothing of the caller's is written before the last step
+  if (!challengers || !proofs || !proof_lens || !verdicts_out) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL argument");
+  if (n_proofs == 0) return set_error(ctx, CP_ERR_INVALID_ARG, "no proofs");
+  if (path_form > PATHS_COOP) return set_error(ctx, CP_ERR_INVALID_ARG, "path_form %u: 0 (chosen by the library), 1 (one lane per path) or 2 (twelve lanes per path)", path_form);
+  StarkShape s;
+  CP_TRY(stark_shape(ctx, desc, false, s));
+  if ((desc->n_public && !publics) || (desc->n_global && !globals)) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL publics / globals");
+  for (size_t i = 0; i < n_proofs; i++) {
+    if (!proofs[i] && proof_lens[i]) return set_error(ctx, CP_ERR_INVALID_ARG, "proof %zu is NULL", i);
+    if (!all_canonical(publics ? publics + i * desc->n_public : nullptr, desc->n_public) ||
+        !all_canonical(globals ? globals + i * desc->n_global : nullptr, desc->n_global))
+      return set_error(ctx, CP_ERR_INVALID_ARG, "proof %zu: a public input / global value is not canonical", i);
+    if (const char *why = challenger_problem(&challengers[i])) return set_error(ctx, CP_ERR_INVALID_ARG, "proof %zu: %s", i, why);
+  }
+  friv::Instance D;
+  FriVerifyInstance I0;
+  size_t proof_words;
+  CP_TRY(stark_layout(ctx, desc, s, I0, D, proof_words));
+  CHECK_CTX(ctx);
+  hostu::alloc_checkpoint();
+  std::vector<cp_challenger_state> ch_out(n_proofs);
+  std::vector<cp_verify_verdict> verdicts(n_proofs);
+  CP_TRY(verify_batch_passes(ctx, D, proof_words, nullptr, proofs, proof_lens, n_proofs, chunk_proofs, (PathForm)path_form, verdicts.data(),
+                             [&](size_t p, uint64_t *rec) {
+                               return stark_verify_host_phase(desc, s, publics ? publics + p * desc->n_public : nullptr,
+                                                              globals ? globals + p * desc->n_global : nullptr, challengers[p], proofs[p], proof_lens[p],
+                                                              ch_out[p], rec);
+                             }));
+  for (size_t i = 0; i < n_proofs; i++) {
+    verdicts_out[i] = verdicts[i];
+    if (verdicts[i].status == 0) challengers[i] = ch_out[i];
+  }
+  return CP_OK;
+} CP_CATCH(ctx)
 
 }  // extern "C"

@@ -686,10 +686,17 @@ size_t verify_threads(size_t n) {
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The passes of a batch. host(p, rec) is the host phase of proof p (any thread; it must not touch ctx or the HIP API): its
-// verdict, and with status 0 the challenge record. shared_cap: 2^cap_height x 4 words on the host, or null.
+// verdict, and with status 0 the challenge record. shared_cap: 2^cap_height x 4 words on the host, or null. path_form: which kernel
+// checks the Merkle paths of a pass (PATHS_AUTO decides per pass by its number of paths).
+enum PathForm : unsigned { PATHS_AUTO = 0, PATHS_LANE = 1, PATHS_COOP = 2 };
+// PATHS_AUTO takes the twelve-lane kernel for passes of fewer than this many paths per tree (active proofs x query rounds). Measured
+// at the SHA-256 STARK's shape (DESIGN.md section 1.1a, profiles/stark_verify_batch.json): the twelve-lane kernel is the faster one up
+// to 10 752 paths per pass (3.1 against 4.2 ms), the lane-per-path kernel from 21 504 on (4.3 against 5.1 ms); the twelve-lane
+// kernel's time between the two, taken as a straight line, meets the other's flat 4.2 ms at about 16 600.
+constexpr size_t PATHS_COOP_BELOW = 16384;
 template <class Host>
 int verify_batch_passes(cp_ctx *ctx, const friv::Instance &D, size_t proof_words, const uint64_t *shared_cap, const uint8_t *const *proofs,
-                        const size_t *lens, size_t n, size_t chunk, cp_verify_verdict *out, Host host) {
+                        const size_t *lens, size_t n, size_t chunk, PathForm path_form, cp_verify_verdict *out, Host host) {
   const size_t L = proof_words * 8, rec_w = friv::rec_words(D.n_batches, D.n_layers, D.n_queries), nq = D.n_queries;
   if (chunk == 0) chunk = VERIFY_BATCH_PASS_BYTES / L ? VERIFY_BATCH_PASS_BYTES / L : 1;
   if (chunk > n) chunk = n;
@@ -752,7 +759,12 @@ int verify_batch_passes(cp_ctx *ctx, const friv::Instance &D, size_t proof_words
     a.n_proofs = (uint32_t)m;
     a.n_queries = (uint32_t)nq;
     const unsigned blocks = blocks_for(m * nq, 64);
-    LAUNCH(ctx, "verify_paths", friv::k_paths, dim3(blocks, D.n_oracles + D.n_layers), dim3(64), a);
+    const bool coop = path_form == PATHS_COOP || (path_form == PATHS_AUTO && n_active * nq < PATHS_COOP_BELOW);
+    if (coop)
+      LAUNCH(ctx, "verify_paths_coop", friv::k_paths_coop, dim3(blocks_for(m * nq, pcoop::STATES_PER_BLOCK), D.n_oracles + D.n_layers),
+             dim3(64 * pcoop::WAVES), a);
+    else
+      LAUNCH(ctx, "verify_paths", friv::k_paths, dim3(blocks, D.n_oracles + D.n_layers), dim3(64), a);
     LAUNCH(ctx, "verify_arith", friv::k_arith, dim3(blocks), dim3(64), a);
     HIP_TRY(ctx, hipMemcpyAsync(st_keys, d_misc + m_keys, m * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, sync_stream(ctx));
@@ -795,7 +807,7 @@ extern "C" int cp_verify_batch(cp_circuit *circ, const uint8_t *const *proofs, c
   CP_TRY(plonky2_layout(ctx, sh, true, D, proof_words));
   std::vector<uint64_t> ks(sh.num_routed_wires);  // once per call, not once per proof
   if (!ks.empty()) HIP_TRY(ctx, hipMemcpy(ks.data(), circ->k_is, ks.size() * 8, hipMemcpyDeviceToHost));
-  return verify_batch_passes(ctx, D, proof_words, circ->cs.cap_host.data(), proofs, proof_lens, n_proofs, chunk_proofs, verdicts_out,
+  return verify_batch_passes(ctx, D, proof_words, circ->cs.cap_host.data(), proofs, proof_lens, n_proofs, chunk_proofs, PATHS_LANE, verdicts_out,
                              [&](size_t p, uint64_t *rec) { return verify_host_phase(*circ, ks.data(), proofs[p], proof_lens[p], rec); });
 } CP_CATCH(circ ? circ->ctx : nullptr)
 
@@ -824,7 +836,7 @@ extern "C" int cp_verify_fri_queries_with_challenges_batch(cp_ctx *ctx, const cp
   friv::Instance D;
   size_t proof_words;
   CP_TRY(plonky2_layout(ctx, sh, cs_cap != nullptr, D, proof_words));
-  return verify_batch_passes(ctx, D, proof_words, cs_cap, proofs, proof_lens, n_proofs, chunk_proofs, verdicts_out, [&](size_t p, uint64_t *rec) {
+  return verify_batch_passes(ctx, D, proof_words, cs_cap, proofs, proof_lens, n_proofs, chunk_proofs, PATHS_LANE, verdicts_out, [&](size_t p, uint64_t *rec) {
     ParsedProof pp;
     if (parse_proof_bytes(nullptr, sh, nullptr, proofs[p], proof_lens[p], pp) != CP_OK) return parse_verdict();
     const gl::Ext alpha{alphas[2 * p], alphas[2 * p + 1]}, zeta{zetas[2 * p], zetas[2 * p + 1]};

@@ -739,6 +739,38 @@ int cp_stark_prove_batch(cp_ctx *ctx, const cp_stark_desc *desc, size_t n_traces
  * 0 = accepted; CP_ERR_VERIFY with cp_last_error(NULL) naming the first failing check. */
 int cp_stark_verify(const cp_stark_desc *desc, const uint64_t *publics, const uint64_t *globals, cp_challenger_state *challenger,
                     const uint8_t *proof, size_t proof_len);
+/* n_proofs proofs of ONE description in one call, the query phase on the device (what cp_verify_batch is to cp_verify). Per proof,
+ * on host threads, exactly what cp_stark_verify does before its query phase (parse, transcript, round challenges, alphas, zeta, the
+ * constraints at zeta against the quotient, the openings into the transcript, FRI challenges, proof of work); the accepted ones are
+ * uploaded and every Merkle path and all the query arithmetic is checked by the kernels of csrc/fri_verify.h.
+ * One verdict per proof, the FIRST failure in cp_stark_verify's own order, in cp_verify_batch's statuses; unused fields are -1:
+ *   status 0  accepted
+ *          1  malformed (any length prefix, truncation, trailing bytes)
+ *          2  an element >= p
+ *          3  not used
+ *          4  zeta in the trace domain, or an opening point on the LDE coset (`query` set in the second case)
+ *          5  quotient identity (`detail` = challenge)
+ *          6  proof of work (a non-canonical witness included)
+ *          7  Merkle path of an oracle (`query`, `detail` = oracle: 0 trace, 1 extended - or quotient when there are no extended
+ *             columns -, 2 quotient)
+ *          8  FRI layer value (`query`, `detail` = layer)
+ *          9  Merkle path of a FRI layer (`query`, `detail` = layer)
+ *         10  final polynomial (`query`)
+ * publics / globals: n_proofs x n_public / n_global (NULL when 0). challengers: n_proofs, in and out: challengers[i] is updated
+ * exactly as cp_stark_verify updates it when proof i is accepted, and left as it came in when it is rejected. proofs[i] may be
+ * unaligned, and NULL where proof_lens[i] is 0. chunk_proofs: as for cp_verify_batch.
+ * path_form: which kernel checks the Merkle paths - CP_PATHS_AUTO chosen by the library per device pass, CP_PATHS_LANE one lane
+ * per path (cp_verify_batch's kernel), CP_PATHS_COOP twelve lanes per path (for few proofs with long leaves).
+ * Returns CP_OK whatever the verdicts are. CP_ERR_INVALID_ARG - checked before the context is looked at, and nothing of the
+ * caller's is written - for NULL arguments, n_proofs == 0, an unknown path_form, a description cp_stark_verify refuses, a
+ * non-canonical public or global value, a malformed incoming challenger, more than 255 query rounds. CP_ERR_OOM for a refused
+ * allocation: no verdict and no challenger is written and the context stays usable. */
+#define CP_PATHS_AUTO 0u
+#define CP_PATHS_LANE 1u
+#define CP_PATHS_COOP 2u
+int cp_stark_verify_batch(cp_ctx *ctx, const cp_stark_desc *desc, size_t n_proofs, const uint64_t *publics, const uint64_t *globals,
+                          cp_challenger_state *challengers, const uint8_t *const *proofs, const size_t *proof_lens,
+                          size_t chunk_proofs, unsigned path_form, cp_verify_verdict *verdicts_out);
 
 /* ---- BLS12-381 G1 multi-scalar multiplication ---------------------------------
  * The G1 MSMs of the Groth16 wrap proof: replaces the CPU MSM inside `gnark_plonky2_wrapper::wrap_plonky2_proof`

@@ -534,3 +534,22 @@ pub fn stark_prove_batch(ctx: &Context, desc: &ffi::CpStarkDesc, traces: &[&[u64
         v
     }).collect())
 }
+
+/// Several proofs of one `cp_stark_desc` verified in one call (`cp_stark_verify_batch`): per proof the host part of
+/// `cp_stark_verify` on host threads, every Merkle path and the query arithmetic on the device. One verdict per proof, the first
+/// failure in `cp_stark_verify`'s order (status 0 = accepted; include/cityprover.h has the table). `publics` / `globals`: every
+/// proof's values in a row. The challenger of an accepted proof is advanced as `cp_stark_verify` advances it, a rejected proof's
+/// is left alone. `path_form`: `ffi::CP_PATHS_AUTO`, `CP_PATHS_LANE` or `CP_PATHS_COOP`; `chunk_proofs`: 0 = the library's.
+pub fn stark_verify_batch(ctx: &Context, desc: &ffi::CpStarkDesc, publics: &[u64], globals: &[u64], challengers: &mut [ffi::CpChallengerState], proofs: &[&[u8]], chunk_proofs: usize, path_form: u32) -> Result<Vec<ffi::CpVerifyVerdict>> {
+    let n = proofs.len();
+    if challengers.len() != n {
+        return Err(anyhow!("stark_verify_batch: {n} proofs, {} challengers", challengers.len()));
+    }
+    let ps: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+    let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+    let mut out = vec![ffi::CpVerifyVerdict { status: -1, query: -1, detail: -1, reserved: 0 }; n];
+    check(ctx.raw, unsafe {
+        ffi::cp_stark_verify_batch(ctx.raw, desc, n, publics.as_ptr(), globals.as_ptr(), challengers.as_mut_ptr(), ps.as_ptr(), lens.as_ptr(), chunk_proofs, path_form as _, out.as_mut_ptr())
+    })?;
+    Ok(out)
+}
