@@ -1178,10 +1178,53 @@ class Groth16Verifier:
         p._check(p.lib.cp_groth16_verify_bls12381(p.ctx, self.handle, _ptr(proofs), None if pub is None else _ptr(pub), n, flags, out.ctypes.data_as(_u8p)))
         return out
 
+    def verify_city(self, blobs, publics=None, flags=0, prover=None):
+        """verify() with the proofs as stored: a sequence of 192-byte strings or an (n, 192) uint8 array
+        (cp_groth16_verify_city_bls12381). A proof that does not decompress gets verdict 2."""
+        p = prover or self.prover
+        blobs = _city_blobs(blobs)
+        n = len(blobs)
+        pub = None
+        if self.n_public > 1:
+            pub = _as_u64(publics).reshape(n, self.n_public - 1, 4)
+        out = np.zeros(n, np.uint8)
+        p._check(p.lib.cp_groth16_verify_city_bls12381(p.ctx, self.handle, blobs.ctypes.data_as(_u8p), None if pub is None else _ptr(pub), n, flags,
+                                                       out.ctypes.data_as(_u8p)))
+        return out
+
     def close(self):
         if self.handle:
             self.prover.lib.cp_groth16_verifier_destroy(self.handle)
             self.handle = None
+
+
+ABI["cp_groth16_proofs_unpack_city_bls12381"] = (ctypes.c_int, [_vp, _u8p, ctypes.c_size_t, _u64p, _u8p])
+ABI["cp_groth16_verify_city_bls12381"] = (ctypes.c_int, [_vp, _vp, _u8p, _u64p, ctypes.c_size_t, ctypes.c_uint, _u8p])
+
+
+def _city_blobs(blobs):
+    """a sequence of 192-byte strings or an (n, 192) uint8 array -> a contiguous (n, 192) uint8 array"""
+    if isinstance(blobs, np.ndarray):
+        a = np.ascontiguousarray(blobs, np.uint8)
+    else:
+        blobs = [bytes(b) for b in blobs]
+        if any(len(b) != 192 for b in blobs):
+            raise ValueError("CityGroth16ProofData is 192 bytes")
+        a = np.frombuffer(b"".join(blobs), dtype=np.uint8).copy()
+    if a.size % 192 or (a.ndim == 2 and a.shape[1] != 192) or a.ndim > 2:
+        raise ValueError("CityGroth16ProofData is 192 bytes")
+    return a.reshape(-1, 192)
+
+
+def groth16_unpack_city_batch(prover, blobs):
+    """cp_groth16_proofs_unpack_city_bls12381: stored proofs (a sequence of 192-byte strings or an (n, 192) uint8 array),
+    decompressed on the device. Returns (coords (n, 48) u64: A | B | C as Groth16Verifier.verify takes them, status (n,) u8:
+    0 ok, 1 a flag bit that may not be set, 2 an x >= p, 3 an x of no point); a proof whose status is not 0 has zero words."""
+    blobs = _city_blobs(blobs)
+    n = len(blobs)
+    coords, status = np.zeros((n, 48), np.uint64), np.zeros(n, np.uint8)
+    prover._check(prover.lib.cp_groth16_proofs_unpack_city_bls12381(prover.ctx, blobs.ctypes.data_as(_u8p), n, _ptr(coords), status.ctypes.data_as(_u8p)))
+    return coords, status
 
 
 # ---- circuit files (N1) and the stored Groth16 proof form ----

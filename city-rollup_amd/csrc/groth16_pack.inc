@@ -12,82 +12,15 @@
 // point on the twist: byte order, flag position and the a0 / a1 order are reference-held facts. What the samples cannot
 // pin is which root the 0x80 flag names; this follows arkworks 0.4 (`y > -y`, F_p^2 compared by c1 then c0).
 // Host-only arithmetic (no GPU): included by bls.hip after msm.inc.
+#include "bls_sqrt.h"
 
 namespace g16pack {
 
-using bls::Fp;
-using bls::Fp2;
-
-Fp fp_pow_words(const Fp &a, const uint32_t e[12]) {
-  Fp r = bls::fp_one();
-  for (int i = 32 * 12 - 1; i >= 0; i--) {
-    r = bls::fp_sqr(r);
-    if ((e[i / 32] >> (i % 32)) & 1) r = bls::fp_mul(r, a);
-  }
-  return r;
-}
-void p_plus(int add, int shift, uint32_t out[12]) {  // (p + add) >> shift, add in {-3, +1}: p ends in ...aaab, no carry / borrow
-  uint32_t w[12];
-  for (int i = 0; i < 12; i++) w[i] = BLS_P32[i];
-  w[0] = (uint32_t)((int64_t)w[0] + add);
-  for (int i = 0; i < 12; i++) out[i] = (w[i] >> shift) | (i + 1 < 12 && shift ? w[i + 1] << (32 - shift) : 0);
-}
-// p = 3 mod 4: a^((p+1)/4) is a root when one exists
-bool fp_sqrt(const Fp &a, Fp *root) {
-  uint32_t e[12];
-  p_plus(1, 2, e);
-  const Fp r = fp_pow_words(a, e);
-  if (!bls::fp_eq(bls::fp_sqr(r), a)) return false;
-  *root = r;
-  return true;
-}
-Fp2 fp2_pow_words(const Fp2 &a, const uint32_t e[12]) {
-  Fp2 r = bls::Field<Fp2>::one();
-  for (int i = 32 * 12 - 1; i >= 0; i--) {
-    r = bls::fp2_sqr(r);
-    if ((e[i / 32] >> (i % 32)) & 1) r = bls::fp2_mul(r, a);
-  }
-  return r;
-}
-// square root in F_p[u]/(u^2+1), p = 3 mod 4 (Adj & Rodriguez-Henriquez, Algorithm 9)
-bool fp2_sqrt(const Fp2 &a, Fp2 *root) {
-  if (bls::f_is_zero(a)) { *root = a; return true; }
-  uint32_t e34[12], e12[12];
-  p_plus(-3, 2, e34);  // (p - 3) / 4
-  p_plus(-1, 1, e12);  // (p - 1) / 2
-  const Fp2 a1 = fp2_pow_words(a, e34);
-  const Fp2 alpha = bls::fp2_mul(bls::fp2_sqr(a1), a);
-  const Fp2 x0 = bls::fp2_mul(a1, a);
-  const Fp2 minus_one = {bls::fp_sub(bls::fp_zero(), bls::fp_one()), bls::fp_zero()};
-  Fp2 r;
-  if (bls::f_eq(alpha, minus_one)) r = bls::fp2_mul(Fp2{bls::fp_zero(), bls::fp_one()}, x0);
-  else r = bls::fp2_mul(fp2_pow_words(bls::fp2_add(bls::Field<Fp2>::one(), alpha), e12), x0);
-  if (!bls::f_eq(bls::fp2_sqr(r), a)) return false;
-  *root = r;
-  return true;
-}
-int cmp_words(const uint32_t *a, const uint32_t *b) {  // 12-word little-endian integers
-  for (int k = 11; k >= 0; k--) {
-    if (a[k] < b[k]) return -1;
-    if (a[k] > b[k]) return 1;
-  }
-  return 0;
-}
-// y > -y ? (canonical integers; for F_p^2: by c1, then c0)
-bool fp_is_larger(const Fp &y) {
-  uint32_t a[12], b[12];
-  bls::fp_to_canonical(y, a);
-  bls::fp_to_canonical(bls::fp_sub(bls::fp_zero(), y), b);
-  return cmp_words(a, b) > 0;
-}
-bool fp2_is_larger(const Fp2 &y) {
-  uint32_t a[12], b[12];
-  bls::fp_to_canonical(y.c1, a);
-  bls::fp_to_canonical(bls::fp_sub(bls::fp_zero(), y.c1), b);
-  const int c = cmp_words(a, b);
-  if (c != 0) return c > 0;
-  return fp_is_larger(y.c0);
-}
+// the square roots and the "larger root" predicates: bls_sqrt.h, shared with the kernels of pairing.hip
+using blssqrt::fp_sqrt;
+using blssqrt::fp2_sqrt;
+using blssqrt::fp_is_larger;
+using blssqrt::fp2_is_larger;
 
 }  // namespace g16pack
 

@@ -1,9 +1,11 @@
 // libcityprover_hip.so, third translation unit: BLS12-381 pairing products and the Groth16 verifier, batched on the device
 // (DESIGN.md section 4.6). The arithmetic is pairing.h; here are the kernels - one lane per item, like k_bucket_sum and
 // fixedbase::k_mul - and the entry points. The work is split into several kernels, none of which holds more than one of
-// the big loops: point checks, the public-input sum, the Miller loop, and the product with the final exponentiation.
+// the big loops: point checks, the public-input sum, the Miller loop, and the product with the final exponentiation. In front of
+// them, for proofs in their stored 192-byte form, the decompression (bls_sqrt.h): one launch for the F_p roots, one for the F_p^2 roots.
 #include "core.h"
 #include "pairing.h"
+#include "bls_sqrt.h"
 #include "bls12_381_fr.h"
 
 namespace pairing {
@@ -129,6 +131,33 @@ __global__ __launch_bounds__(LANES) void k_final(const uint32_t *__restrict__ mi
     for (int c = 0; c < 6; c++) bls::Field<Fp2>::to_canonical(f12_get(f, c), (uint32_t *)(gt + j * CP_GT_WORDS + 12 * c));
 }
 
+// ---- the stored proof form: n x 192 bytes, pi_a | pi_b_a0 | pi_b_a1 | pi_c, each a compressed point (bls_sqrt.h) ----
+// One lane per element, the F_p elements and the F_p^2 element in launches of their own: a wave never mixes the one
+// exponentiation of a G1 root with the two of a G2 root. Lane e of k_unpack_g1 takes pi_a (e even) or pi_c (e odd) of proof
+// e / 2 and writes x | y into words 0 .. 11 or 36 .. 47 of the proof's 48 u64 of `out` (A | B | C, affine canonical, what
+// verify_run stages) and its status class into est[e].
+__global__ __launch_bounds__(LANES) void k_unpack_g1(const uint32_t *__restrict__ city, size_t n, uint64_t *__restrict__ out, uint8_t *__restrict__ est) {
+  const size_t e = (size_t)blockIdx.x * LANES + threadIdx.x;
+  if (e >= 2 * n) return;
+  const size_t t = e >> 1, c = e & 1;
+  est[e] = (uint8_t)blssqrt::g1_decompress(city + t * 48 + 36 * c, (uint32_t *)(out + t * 48 + 36 * c));
+}
+// Lane t takes pi_b of proof t into words 12 .. 35, then closes the proof (the G1 launch is before it on the stream):
+// status[t] = the smallest class that applies to any of the three elements, and a proof whose status is not 0 gets 48 zero words.
+__global__ __launch_bounds__(LANES) void k_unpack_g2(const uint32_t *__restrict__ city, size_t n, uint64_t *__restrict__ out, const uint8_t *__restrict__ est,
+                                                     uint8_t *__restrict__ status) {
+  const size_t t = (size_t)blockIdx.x * LANES + threadIdx.x;
+  if (t >= n) return;
+  int st = blssqrt::g2_decompress(city + t * 48 + 12, (uint32_t *)(out + t * 48 + 12));
+  for (int c = 0; c < 2; c++) {
+    const int s = est[2 * t + c];
+    if (s && (!st || s < st)) st = s;
+  }
+  status[t] = (uint8_t)st;
+  if (st)
+    for (int w = 0; w < 48; w++) out[t * 48 + w] = 0;
+}
+
 }  // namespace pairing
 
 struct cp_groth16_verifier {
@@ -162,6 +191,18 @@ struct Carve {
 };
 constexpr size_t MAX_PAIRS = (size_t)1 << 24;
 
+// the device arrays of n proofs in their stored form
+struct City {
+  uint8_t *bytes = nullptr;   // n x 192, as they came
+  uint8_t *est = nullptr;     // 2 n: the status classes of pi_a and pi_c
+  uint8_t *status = nullptr;  // n: of the proof
+  void carve(Carve &c, size_t n) {
+    bytes = c.take<uint8_t>(n * 192);
+    est = c.take<uint8_t>(2 * n);
+    status = c.take<uint8_t>(n);
+  }
+};
+
 // the device arrays of a batch of pairs and products
 struct Batch {
   size_t n_pairs = 0, n = 0, k = 0;
@@ -173,7 +214,8 @@ struct Batch {
   uint32_t *miller = nullptr, *tmp = nullptr, *work = nullptr;
   uint64_t *gt = nullptr;
   uint8_t *is_one = nullptr, *status = nullptr;
-  void carve(Carve &c, size_t g1_words, size_t g2_words, size_t pub_words, bool flags1, bool flags2, bool want_gt) {
+  City city;  // the verifier's proofs in their stored form (city_proofs of them), else unused
+  void carve(Carve &c, size_t g1_words, size_t g2_words, size_t pub_words, bool flags1, bool flags2, bool want_gt, size_t city_proofs = 0) {
     g1_xy = c.take<uint64_t>(g1_words * 8);
     g2_xy = c.take<uint64_t>(g2_words * 8);
     publics = pub_words ? c.take<uint64_t>(pub_words * 8) : nullptr;
@@ -190,15 +232,46 @@ struct Batch {
     gt = want_gt ? c.take<uint64_t>(n * CP_GT_WORDS * 8) : nullptr;
     is_one = c.take<uint8_t>(n);
     status = c.take<uint8_t>(n);
+    if (city_proofs) city.carve(c, city_proofs);
   }
 };
 
-int batch_alloc(cp_ctx *ctx, DevBag &bag, Batch &b, size_t g1_words, size_t g2_words, size_t pub_words, bool flags1, bool flags2, bool want_gt) {
+int batch_alloc(cp_ctx *ctx, DevBag &bag, Batch &b, size_t g1_words, size_t g2_words, size_t pub_words, bool flags1, bool flags2, bool want_gt,
+                size_t city_proofs = 0) {
   Carve size;
-  b.carve(size, g1_words, g2_words, pub_words, flags1, flags2, want_gt);
+  b.carve(size, g1_words, g2_words, pub_words, flags1, flags2, want_gt, city_proofs);
   Carve c;
   CP_TRY(alloc_status(ctx, bag.alloc(&c.base, size.off), size.off));
-  b.carve(c, g1_words, g2_words, pub_words, flags1, flags2, want_gt);
+  b.carve(c, g1_words, g2_words, pub_words, flags1, flags2, want_gt, city_proofs);
+  return CP_OK;
+}
+
+// n stored proofs on the device (c.bytes) -> n x 48 u64 at `out` and c.status
+int city_unpack(cp_ctx *ctx, const City &c, size_t n, uint64_t *out) {
+  using namespace pairing;
+  LAUNCH(ctx, "groth16_unpack_g1", k_unpack_g1, dim3(blocks_for(2 * n, LANES)), dim3(LANES), (const uint32_t *)c.bytes, n, out, c.est);
+  LAUNCH(ctx, "groth16_unpack_g2", k_unpack_g2, dim3(blocks_for(n, LANES)), dim3(LANES), (const uint32_t *)c.bytes, n, out, (const uint8_t *)c.est, c.status);
+  return CP_OK;
+}
+
+int city_unpack_run(cp_ctx *ctx, const uint8_t *proofs, size_t n, uint64_t *proofs_out, uint8_t *status_out) {
+  if (!proofs || !proofs_out || !status_out) return set_error(ctx, CP_ERR_INVALID_ARG, "unpack: NULL argument");
+  if (n == 0) return set_error(ctx, CP_ERR_INVALID_ARG, "unpack: n_proofs must be at least 1");
+  if (n > MAX_PAIRS / 3) return set_error(ctx, CP_ERR_INVALID_ARG, "unpack: more than 2^24 / 3 proofs in one call");
+  City city;
+  Carve size;  // one allocation, as in batch_alloc: a size pass, then a pointer pass
+  city.carve(size, n);
+  size.take<uint64_t>(n * 48 * 8);
+  DevBag bag = ctx->bag();
+  Carve c;
+  CP_TRY(alloc_status(ctx, bag.alloc(&c.base, size.off), size.off));
+  city.carve(c, n);
+  uint64_t *out = c.take<uint64_t>(n * 48 * 8);
+  HIP_TRY(ctx, hipMemcpyAsync(city.bytes, proofs, n * 192, hipMemcpyHostToDevice, ctx->stream));
+  CP_TRY(city_unpack(ctx, city, n, out));
+  HIP_TRY(ctx, hipMemcpyAsync(proofs_out, out, n * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(status_out, city.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, sync_stream(ctx));
   return CP_OK;
 }
 
@@ -292,7 +365,10 @@ int verifier_build(cp_ctx *ctx, const cp_groth16_vk *vk, const uint64_t *ic_xy, 
   return CP_OK;
 }
 
-int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const uint64_t *proofs, const uint64_t *publics, size_t n, unsigned flags, uint8_t *verdict_out) {
+// proofs: n x 48 u64 of coordinates (city = false) or n x 192 bytes in the stored form (city = true), which are decompressed on
+// the device into the same staging array: a proof refused there is 48 zero words, on neither the curve nor the twist, and
+// gets verdict 2 from the point checks like any other bad point.
+int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bool city, const uint64_t *publics, size_t n, unsigned flags, uint8_t *verdict_out) {
   using namespace pairing;
   if (!v) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: the verifier is NULL");
   if (v->device != ctx->device) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: the verifier lives on device %d, the context on device %d", v->device, ctx->device);
@@ -306,9 +382,14 @@ int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const uint64_t *proofs
   b.n = n; b.k = 3; b.n_pairs = 3 * n;
   const size_t pub_words = n * (v->n_public - 1) * 4;
   DevBag bag = ctx->bag();
-  CP_TRY(batch_alloc(ctx, bag, b, n * 48, 0, pub_words, true, false, false));
-  uint64_t *pr = b.g1_xy;  // the proofs as they came: A | B | C
-  HIP_TRY(ctx, hipMemcpyAsync(pr, proofs, n * 48 * 8, hipMemcpyHostToDevice, ctx->stream));
+  CP_TRY(batch_alloc(ctx, bag, b, n * 48, 0, pub_words, true, false, false, city ? n : 0));
+  uint64_t *pr = b.g1_xy;  // the proofs as coordinates: A | B | C
+  if (city) {
+    HIP_TRY(ctx, hipMemcpyAsync(b.city.bytes, proofs, n * 192, hipMemcpyHostToDevice, ctx->stream));
+    CP_TRY(city_unpack(ctx, b.city, n, pr));
+  } else {
+    HIP_TRY(ctx, hipMemcpyAsync(pr, proofs, n * 48 * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
   if (pub_words) HIP_TRY(ctx, hipMemcpyAsync(b.publics, publics, pub_words * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(b.inf1, 0, b.n_pairs, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(b.st1, 0, b.n_pairs, ctx->stream));
@@ -358,7 +439,18 @@ void cp_groth16_verifier_destroy(cp_groth16_verifier *v) try {
 int cp_groth16_verify_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint64_t *proofs_host, const uint64_t *public_inputs_host, size_t n_proofs,
                                unsigned flags, uint8_t *verdict_out_host) try {
   CHECK_CTX(ctx);
-  return verify_run(ctx, v, proofs_host, public_inputs_host, n_proofs, flags, verdict_out_host);
+  return verify_run(ctx, v, proofs_host, false, public_inputs_host, n_proofs, flags, verdict_out_host);
+} CP_CATCH(ctx)
+
+int cp_groth16_verify_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint8_t *proofs_host, const uint64_t *public_inputs_host, size_t n_proofs,
+                                    unsigned flags, uint8_t *verdict_out_host) try {
+  CHECK_CTX(ctx);
+  return verify_run(ctx, v, proofs_host, true, public_inputs_host, n_proofs, flags, verdict_out_host);
+} CP_CATCH(ctx)
+
+int cp_groth16_proofs_unpack_city_bls12381(cp_ctx *ctx, const uint8_t *proofs_host, size_t n_proofs, uint64_t *proofs_out_host, uint8_t *status_out_host) try {
+  CHECK_CTX(ctx);
+  return city_unpack_run(ctx, proofs_host, n_proofs, proofs_out_host, status_out_host);
 } CP_CATCH(ctx)
 
 }  // extern "C"

@@ -1019,6 +1019,26 @@ int cp_groth16_proof_pack_city(const uint64_t a_xy[12], const uint64_t b_xy[24],
 /* the inverse (decompression: one square root per element); refuses x that is not on the curve / twist */
 int cp_groth16_proof_unpack_city(const uint8_t in[192], uint64_t a_xy[12], uint64_t b_xy[24], uint64_t c_xy[12]);
 
+/* The stored form in batches, decompressed on the device: one lane per element takes the square root (F_p for pi_a and pi_c,
+ * F_p^2 for pi_b).
+ * cp_groth16_proofs_unpack_city_bls12381: proofs_host: n_proofs x 192 bytes. proofs_out_host: n_proofs x 48 u64, A (12) |
+ * B (24) | C (12), affine canonical - what cp_groth16_verify_bls12381 takes. status_out_host, per proof, the smallest class that
+ * applies anywhere in the proof: 0 ok; 1 a flag bit that may not be set (0x40 on pi_a, pi_b_a1 or pi_c, any flag bit on
+ * pi_b_a0); 2 an x, or a half of pi_b's x, that is >= p after the flags are masked; 3 an x that is the abscissa of no point
+ * of the curve / twist. A proof whose status is not 0 gets 48 zero words; the call still returns CP_OK: a bad proof is a
+ * verdict on its item. Status is 0 exactly where cp_groth16_proof_unpack_city returns CP_OK, and the words are then that
+ * function's; like it, this makes no subgroup check. CP_ERR_INVALID_ARG: a NULL argument, n_proofs = 0, more than 2^24 / 3
+ * proofs. A refused allocation is CP_ERR_OOM and the context stays usable.
+ * cp_groth16_verify_city_bls12381: cp_groth16_verify_bls12381 with proofs_host as n_proofs x 192 bytes: half the bytes cross
+ * the bus, and the decompression runs in front of the point checks in the same call. Everything said of that function
+ * holds: the verdicts, CP_PAIRING_TRUSTED, the refusals, the verifier serving any context of its device. A proof whose
+ * unpack status is not 0 gets verdict 2. */
+int cp_groth16_proofs_unpack_city_bls12381(cp_ctx *ctx, const uint8_t *proofs_host, size_t n_proofs,
+                                           uint64_t *proofs_out_host, uint8_t *status_out_host);
+int cp_groth16_verify_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint8_t *proofs_host,
+                                    const uint64_t *public_inputs_host, size_t n_proofs, unsigned flags,
+                                    uint8_t *verdict_out_host);
+
 #ifdef __cplusplus
 }
 #endif

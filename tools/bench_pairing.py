@@ -9,7 +9,10 @@ of the public inputs, which are full width). Per batch size, with and without CP
                  rate they give over the summed kernel time
 The same for bare pairings (k = 1). Prints one JSON line and writes profiles/pairing.json.
 
-usage: bench_pairing.py [batch sizes, comma separated: default 1,64,4096,65536] [--reps N]"""
+With --city, instead: the stored 192-byte form at the same batch sizes (run_city below), written to profiles/pairing_city.json.
+
+usage: bench_pairing.py [batch sizes, comma separated: default 1,64,4096,65536] [--reps N] [--city]"""
+import ctypes
 import json
 import os
 import sys
@@ -74,6 +77,102 @@ def make_key_and_proofs(prover, pool=64):
     return verifier, np.stack(proofs), np.stack(pubs)
 
 
+HOST_LOOP_CAP = 1024   # proofs the host loop of --city decompresses per repeat (about half a millisecond each, one thread)
+
+
+def words_to_proof(w):
+    val = lambda x: sum(int(v) << (64 * j) for j, v in enumerate(x))
+    return (val(w[0:6]), val(w[6:12])), ((val(w[12:18]), val(w[18:24])), (val(w[24:30]), val(w[30:36]))), (val(w[36:42]), val(w[42:48]))
+
+
+def run_city(prover, verifier, proofs, pubs, n, reps):
+    """The stored form (4 x 48 bytes a proof) at batch size n, all in this process, the legs alternating within a repeat:
+      a  verify on coordinates that are already unpacked (the path that existed before the stored form was taken on the device)
+      b  a host loop of cp_groth16_proof_unpack_city, alone, and followed by a: what a holder of stored proofs did before
+      c  verify_city
+      d  the device unpack alone (cp_groth16_proofs_unpack_city_bls12381)
+    The host loop runs over min(n, HOST_LOOP_CAP) proofs and is scaled to n (its time per proof does not depend on n)."""
+    lib = prover.lib
+    u8p, u64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)
+    blobs64 = np.stack([np.frombuffer(cp.groth16_pack_city(*words_to_proof(w)), np.uint8) for w in proofs])
+    idx = np.arange(n) % len(proofs)
+    pr, pu, bl = np.ascontiguousarray(proofs[idx]), np.ascontiguousarray(pubs[idx]), np.ascontiguousarray(blobs64[idx])
+    n_host = min(n, HOST_LOOP_CAP)
+    host_out = np.zeros((n_host, 48), np.uint64)
+
+    def host_loop():
+        for i in range(n_host):
+            row = host_out[i]
+            rc = lib.cp_groth16_proof_unpack_city(bl[i].ctypes.data_as(u8p), row[0:12].ctypes.data_as(u64p), row[12:36].ctypes.data_as(u64p),
+                                                  row[36:48].ctypes.data_as(u64p))
+            assert rc == 0
+
+    def a():
+        assert not verifier.verify(pr, pu).any()
+
+    def c():
+        assert not verifier.verify_city(bl, pu).any()
+
+    def d():
+        coords, status = cp.groth16_unpack_city_batch(prover, bl)
+        assert not status.any()
+        return coords
+
+    assert (d() == pr).all()                                     # the same proofs on every path
+    host_loop()
+    assert (host_out == pr[:n_host]).all()
+    legs = {"a_verify_unpacked": a, "b_host_unpack_loop": host_loop, "c_verify_city": c, "d_device_unpack": d}
+    for f in legs.values():
+        f()                                                      # warm-up of every shape
+    walls = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, f in legs.items():
+            t0 = time.perf_counter()
+            f()
+            walls[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in walls.items()}
+    out = {"n": n, "reps": reps, "wall_ms": {k: {"median": round(med[k], 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in walls.items()}}
+    host_per_proof_us = med["b_host_unpack_loop"] / n_host * 1e3
+    b_total = host_per_proof_us * n / 1e3
+    out["b_host_loop"] = {"proofs_timed": n_host, "us_per_proof": round(host_per_proof_us, 2), "ms_scaled_to_n": round(b_total, 3),
+                          "then_a_ms": round(b_total + med["a_verify_unpacked"], 3), "then_a_is": "the sum of the two medians"}
+    out["us_per_proof"] = {"a": round(med["a_verify_unpacked"] / n * 1e3, 3), "b_then_a": round((b_total + med["a_verify_unpacked"]) / n * 1e3, 3),
+                           "c": round(med["c_verify_city"] / n * 1e3, 3), "d": round(med["d_device_unpack"] / n * 1e3, 3)}
+    out["c_over_a"] = round(med["c_verify_city"] / med["a_verify_unpacked"], 4)
+    out["c_minus_a_us_per_proof"] = round((med["c_verify_city"] - med["a_verify_unpacked"]) / n * 1e3, 3)
+    out["b_then_a_over_c"] = round((b_total + med["a_verify_unpacked"]) / med["c_verify_city"], 3)
+    prover.profile_begin()
+    c()
+    prof = prover.profile_end()
+    out["c_kernels_ms"] = {k: round(v["total_ms"], 4) for k, v in prof.items() if k.startswith(("pairing_", "groth16_unpack_"))}
+    return out
+
+
+def main_city(sizes, reps):
+    p = cp.Prover(0)
+    out = {"tool": "tools/bench_pairing.py --city", "method": "one process; per batch size every leg is warmed up once, then the legs alternate within each "
+           "of `reps` repeats; wall = host clock around the synchronous call (staging and result copies included); the host loop is timed over "
+           "min(n, %d) proofs and scaled to n; kernels = device events of one further profiled verify_city call" % HOST_LOOP_CAP,
+           "n_public": N_PUBLIC, "kernel_registers": None, "sizes": []}
+    try:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import kernel_meta
+        out["kernel_registers"] = [{k: r[k] for k in ("name", "vgpr", "agpr", "vgpr_spill", "scratch", "lds")} for r in kernel_meta.kernels() if "k_unpack" in r["name"]]
+    except Exception as e:
+        out["kernel_registers"] = "unavailable: %s" % e
+    verifier, proofs, pubs = make_key_and_proofs(p)
+    for n in sizes:
+        out["sizes"].append(run_city(p, verifier, proofs, pubs, n, reps))
+        print("city", json.dumps(out["sizes"][-1]), flush=True)
+    verifier.close()
+    p.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "pairing_city.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def measure(prover, call, reps, n, products):
     call()                                   # warm-up
     wall = []
@@ -111,6 +210,9 @@ if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     sizes = [int(x) for x in (args[0] if args else "1,64,4096,65536").split(",")]
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
+    if "--city" in sys.argv:
+        main_city(sizes, reps)
+        sys.exit(0)
     p = cp.Prover(0)
     counts = fp_product_counts()
     out = {"tool": "tools/bench_pairing.py", "method": "one warm-up call; wall = host clock around the synchronous call (staging and verdict copies included), "
