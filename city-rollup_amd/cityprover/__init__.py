@@ -54,6 +54,7 @@ ABI = {
                                   ctypes.c_size_t]),
     "cp_poseidon_permute_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "cp_field_mul": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, ctypes.c_size_t]),
+    "cp_field_mul2": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, ctypes.c_size_t]),
     "cp_poseidon_permute": (ctypes.c_int, [_vp, _u64p, ctypes.c_size_t]),
     "cp_hash_no_pad": (ctypes.c_int, [_vp, _u64p, ctypes.c_size_t, ctypes.c_size_t, _u64p]),
     "cp_two_to_one": (ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_size_t, _u64p]),
@@ -291,6 +292,14 @@ class Prover:
         out = np.zeros(x.size, np.uint64)
         self._check(self.lib.cp_field_mul(self.ctx, _ptr(x), _ptr(y), _ptr(out), x.size))
         return out
+
+    def field_mul2(self, a, b, c, d):
+        """(a * b, c * d) mod p element-wise with the device's paired product (one lane computes both); any u64 in."""
+        v = [_as_u64(x).ravel().copy() for x in (a, b, c, d)]
+        assert all(x.size == v[0].size for x in v)
+        out_ab, out_cd = np.zeros(v[0].size, np.uint64), np.zeros(v[0].size, np.uint64)
+        self._check(self.lib.cp_field_mul2(self.ctx, _ptr(v[0]), _ptr(v[1]), _ptr(v[2]), _ptr(v[3]), _ptr(out_ab), _ptr(out_cd), v[0].size))
+        return out_ab, out_cd
 
     def poseidon_permute(self, states):
         s = _as_u64(states).copy()

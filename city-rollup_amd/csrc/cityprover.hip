@@ -784,6 +784,37 @@ int cp_field_mul(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, ui
   return cp_d2h(ctx, out_host, o, bytes);
 } CP_CATCH(ctx)
 
+// the paired product (gl::mul_lazy2): one lane computes a b and c d together
+__global__ __launch_bounds__(256) void k_field_mul2(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b,
+                                                    const uint64_t *__restrict__ c, const uint64_t *__restrict__ d,
+                                                    uint64_t *__restrict__ out_ab, uint64_t *__restrict__ out_cd, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    uint64_t r0, r1;
+    gl::mul_lazy2(a[i], b[i], c[i], d[i], r0, r1);
+    out_ab[i] = gl::canon(r0);
+    out_cd[i] = gl::canon(r1);
+  }
+}
+
+int cp_field_mul2(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, const uint64_t *c_host, const uint64_t *d_host,
+                  uint64_t *out_ab_host, uint64_t *out_cd_host, size_t count) try {
+  CHECK_CTX(ctx);
+  if (count == 0) return CP_OK;
+  if (!a_host || !b_host || !c_host || !d_host || !out_ab_host || !out_cd_host) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL pointer");
+  if (count > ((size_t)1 << 27)) return set_error(ctx, CP_ERR_INVALID_ARG, "count too large");
+  const size_t bytes = count * sizeof(uint64_t);
+  CP_TRY(ensure_scratch(ctx, 6 * bytes));
+  uint64_t *a = ctx->scratch.get<uint64_t>(), *b = a + count, *c = b + count, *d = c + count, *o0 = d + count, *o1 = o0 + count;
+  CP_TRY(cp_h2d(ctx, a, a_host, bytes));
+  CP_TRY(cp_h2d(ctx, b, b_host, bytes));
+  CP_TRY(cp_h2d(ctx, c, c_host, bytes));
+  CP_TRY(cp_h2d(ctx, d, d_host, bytes));
+  LAUNCH(ctx, "field_mul2", k_field_mul2, dim3(blocks_for(count, 256)), dim3(256), a, b, c, d, o0, o1, count);
+  CP_TRY(cp_d2h(ctx, out_ab_host, o0, bytes));
+  return cp_d2h(ctx, out_cd_host, o1, bytes);
+} CP_CATCH(ctx)
+
 // ---- Poseidon -------------------------------------------------------------------------------
 
 int cp_poseidon_permute_dev(cp_ctx *ctx, uint64_t *states, size_t count) try {

@@ -200,6 +200,76 @@ GL_HD uint64_t mul_lazy(uint64_t a, uint64_t b) {
   mul_wide_cy(a, b, lo, hi, cy);
   return reduce128_lazy(lo, hi, cy);
 }
+// Two independent products in one go: r0 == a0 b0, r1 == a1 b1, any u64 in, lazy u64 out; each is the arithmetic of `mul_lazy`, bit
+// for bit. What the pair buys is scheduling, not instructions (2 x 11 VALU as before). A lone `mul_lazy` is three basic blocks (its
+// rare-borrow branch) and carries three `s_nop 1` in front of dependent instructions, so one wave's own stream — a SIMD that holds one
+// or two waves — stalls on every product. Here the two chains are issued alternately, so that each VALU write of an SGPR (cy, the
+// low-word borrow, the 64-bit borrow, the fold's carry-out) has its sibling's instruction as the first of the two wait states gfx950
+// needs before a VALU reads that SGPR (counted as LLVM's hazard recogniser counts: one per intervening instruction), and an `s_nop 0`
+// where a second one is missing; the two borrow masks are ORed on the scalar side and tested ONCE, and both chains are repaired behind
+// that single rare, wave-uniform branch (`v_cndmask` on a zero mask selects 0: the chain that did not borrow is left as it is, notes
+// (1)-(4) above `fold_top` hold per chain). Per pair: one branch instead of two, 4 wait states of `s_nop` instead of 12.
+GL_HD void mul_lazy2(uint64_t a0, uint64_t b0, uint64_t a1, uint64_t b1, uint64_t &r0, uint64_t &r1) {
+#if GL_DEVICE_ASM
+  const uint32_t al = lo32(a0), ah = hi32(a0), bl = lo32(b0), bh = hi32(b0);
+  const uint32_t cl = lo32(a1), ch = hi32(a1), dl = lo32(b1), dh = hi32(b1);
+  const uint64_t p00 = (uint64_t)al * bl, q00 = (uint64_t)cl * dl;
+  const uint64_t p01 = (uint64_t)al * bh + (p00 >> 32), q01 = (uint64_t)cl * dh + (q00 >> 32);  // < 2^64
+  // the third multiply-adds; their carry-outs stay in SGPR pairs (`mul_wide_cy`)
+  uint64_t rA, rB;
+  carry_t cyA, cyB;
+  asm("v_mad_u64_u32 %0, %1, %4, %5, %6\n\tv_mad_u64_u32 %2, %3, %7, %8, %9"
+      : "=&v"(rA), "=&s"(cyA), "=&v"(rB), "=&s"(cyB)
+      : "v"(ah), "v"(bl), "v"(p01), "v"(ch), "v"(dl), "v"(q01));
+  const uint64_t loA = pack(lo32(p00), lo32(rA)), loB = pack(lo32(q00), lo32(rB));
+  const uint64_t hiA = (uint64_t)ah * bh + (uint64_t)hi32(rA), hiB = (uint64_t)ch * dh + (uint64_t)hi32(rB);  // (1): no carry
+  // the borrow chains lo - (hi32(hi') + cy). Wait states:
+  //   cyA, cyB come from the statement above, out of the recogniser's sight: the `s_nop 1` in front pads both reads in full;
+  //   low-word borrow of A (%4): written by the 1st subtract, read by the 3rd: the 2nd subtract (chain B) + `s_nop 0`;
+  //   low-word borrow of B (%5): written by the 2nd subtract, read by the 4th: `s_nop 0` + the 3rd subtract (chain A);
+  //   the 64-bit borrows are read next by `s_or_b64` (SALU: no wait states) and, behind the branch, by the repair below.
+  uint32_t tlA, thA, tlB, thB;
+  uint64_t bA, bB, bm;
+  asm("s_nop 1\n\t"
+      "v_subb_co_u32_e64 %0, %4, %7, %8, %10\n\t"
+      "v_subb_co_u32_e64 %2, %5, %11, %12, %14\n\t"
+      "s_nop 0\n\t"
+      "v_subbrev_co_u32_e64 %1, %4, 0, %9, %4\n\t"
+      "v_subbrev_co_u32_e64 %3, %5, 0, %13, %5\n\t"
+      "s_or_b64 %6, %4, %5"
+      : "=&v"(tlA), "=&v"(thA), "=&v"(tlB), "=&v"(thB), "=&s"(bA), "=&s"(bB), "=&s"(bm)
+      : "v"(lo32(loA)), "v"(hi32(hiA)), "v"(hi32(loA)), "s"(cyA), "v"(lo32(loB)), "v"(hi32(hiB)), "v"(hi32(loB)), "s"(cyB)
+      : "scc");
+  uint64_t tA = pack(tlA, thA), tB = pack(tlB, thB);
+  if (__builtin_expect(bm != 0, 0)) {  // (3): a 2^-32 event per product; a chain whose mask is zero subtracts 0
+    uint32_t nA, nB;
+    // bA, bB were written in another statement: the whole pad in front (the compare and the branch between count, but are not in sight)
+    asm volatile("s_nop 1\n\tv_cndmask_b32 %0, 0, -1, %2\n\tv_cndmask_b32 %1, 0, -1, %3" : "=&v"(nA), "=v"(nB) : "s"(bA), "s"(bB));
+    tA -= nA;
+    tB -= nB;
+  }
+  // the folds t0 + w2 (2^32 - 1) (`fold_top`). Wait states of the carry-outs:
+  //   A (%1): written by the 1st multiply-add, read by the 1st select: the 2nd multiply-add (chain B) + `s_nop 0`;
+  //   B (%4): written by the 2nd multiply-add, read by the 2nd select: `s_nop 0` + the 1st select (chain A).
+  // The repair + (2^32 - 1) of chain A is the 64-bit add of `fold_top` (its mask, zero-extended, shares the kernel's one zero register);
+  // chain B's mask would need a second zero register and a move per pair, so its repair is one more multiply-add, bit (0 / 1) times
+  // 2^32 - 1 plus the sum: the same value, and the pair stays at 22 instructions.
+  uint64_t fA, fB, cA, cB, cD;
+  uint32_t mA, nB;
+  asm("v_mad_u64_u32 %0, %1, %8, -1, %9\n\t"
+      "v_mad_u64_u32 %3, %4, %10, -1, %11\n\t"
+      "s_nop 0\n\t"
+      "v_cndmask_b32 %2, 0, -1, %1\n\t"
+      "v_cndmask_b32 %5, 0, 1, %4\n\t"
+      "v_mad_u64_u32 %6, %7, %5, -1, %3"
+      : "=&v"(fA), "=&s"(cA), "=&v"(mA), "=&v"(fB), "=&s"(cB), "=&v"(nB), "=&v"(r1), "=&s"(cD)
+      : "v"(lo32(hiA)), "v"(tA), "v"(lo32(hiB)), "v"(tB));
+  r0 = fA + mA;  // (4): neither can wrap again
+#else
+  r0 = mul_lazy(a0, b0);
+  r1 = mul_lazy(a1, b1);
+#endif
+}
 GL_HD uint64_t mul(uint64_t a, uint64_t b) {
   uint64_t lo, hi;
   carry_t cy;

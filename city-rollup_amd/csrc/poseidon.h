@@ -28,6 +28,7 @@ constexpr int RATE = 8;
 constexpr int HALF_FULL = 4;
 constexpr int PARTIAL = 22;
 constexpr int ROUNDS = 2 * HALF_FULL + PARTIAL;
+static_assert(RATE % 2 == 0 && W % 2 == 0, "the S-boxes of a round go in pairs (sbox_lazy2)");
 
 // device copy of the round constants (uniform index -> scalar loads)
 __constant__ uint64_t d_RC[ROUNDS * W];
@@ -96,7 +97,26 @@ enum : int {
 // ---- lazy field helpers: inputs/outputs are arbitrary u64 congruent to the value ----------
 using gl::fold_top;
 using gl::mul_lazy;
+using gl::mul_lazy2;
+// x^7 = x^3 x^4: x^3 and x^4 are one pair of products (`gl::mul_lazy2`), so an S-box is three products deep, not four
 GL_HD uint64_t sbox_lazy(uint64_t x) {
+  const uint64_t x2 = mul_lazy(x, x);
+  uint64_t x3, x4;
+  mul_lazy2(x, x2, x2, x2, x3, x4);
+  return mul_lazy(x3, x4);
+}
+// two S-boxes, every product of one paired with the same product of the other: what a round does to several words
+GL_HD void sbox_lazy2(uint64_t &x, uint64_t &y) {
+  uint64_t x2, y2, x3, y3, x4, y4;
+  mul_lazy2(x, x, y, y, x2, y2);
+  mul_lazy2(x, x2, y, y2, x3, y3);
+  mul_lazy2(x2, x2, y2, y2, x4, y4);
+  mul_lazy2(x3, x4, y3, y4, x, y);
+}
+// The S-box of the partial rounds (`partial_rounds`), one product after the other: there the two limb planes of the state are live
+// (48 registers) and the pair's second set of temporaries is what does not fit — with `sbox_lazy` the leaf hash (96 registers) spills
+// 7 registers where it spills 6 and k_level grows from 96 registers to 98, a resident wave less.
+GL_HD uint64_t sbox_lazy_chain(uint64_t x) {
   const uint64_t x2 = mul_lazy(x, x), x4 = mul_lazy(x2, x2), x3 = mul_lazy(x, x2);
   return mul_lazy(x3, x4);
 }
@@ -491,7 +511,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
   auto round = [&](int i, double (&al)[W], double (&ah)[W], double (&bl)[W], double (&bh)[W], bool normalise) {
     const double zl = al[0] + al[3] + al[6], zh = ah[0] + ah[3] + ah[6];
     // element 0 of the state: E0 + F0 + v0 + the diagonal 8 of the MDS on the previous S-box output
-    const uint64_t x = sbox_lazy(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
+    const uint64_t x = sbox_lazy_chain(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
     nl = (double)(uint32_t)x;
     nh = (double)(uint32_t)(x >> 32);
     const double dl = __builtin_fma(nl, U, -zl), dh = __builtin_fma(nh, U, -zh);
@@ -524,7 +544,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
     // round i: element 0 = E0 + F0 + v0 + the diagonal 8 of the MDS on the previous S-box output
     {
       const double zl = al[0] + al[3] + al[6], zh = ah[0] + ah[3] + ah[6];
-      const uint64_t x = sbox_lazy(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
+      const uint64_t x = sbox_lazy_chain(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
       nl = (double)(uint32_t)x;
       nh = (double)(uint32_t)(x >> 32);
       const double dl = __builtin_fma(nl, U, -zl), dh = __builtin_fma(nh, U, -zh);
@@ -536,7 +556,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
     for (int k = 0; k < W; k++) renorm_planes_d(al[k], ah[k]);
     // round i + 1: element 0 one layer ahead, then the squared layer with the change of element 0 carried one layer on (a -> b)
     const double zl = dom_next_z(al), zh = dom_next_z(ah);
-    const uint64_t x = sbox_lazy(input(i + 1, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i + 1))));
+    const uint64_t x = sbox_lazy_chain(input(i + 1, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i + 1))));
     nl = (double)(uint32_t)x;
     nh = (double)(uint32_t)(x >> 32);
     dom_mul2_d(al, __builtin_fma(nl, U, -zl), bl);
@@ -581,15 +601,15 @@ GL_HD bool permute_until(uint64_t (&s)[W], Stop stop) {
   for (int r = 0; r < HALF_FULL - 1; r++) {
     if (stop()) return false;
 #pragma unroll
-    for (int i = 0; i < RATE; i++) s[i] = sbox_lazy(s[i]);
+    for (int i = 0; i < RATE; i += 2) sbox_lazy2(s[i], s[i + 1]);
     if (r > 0 || !ZERO_CAP) {
 #pragma unroll
-      for (int i = RATE; i < W; i++) s[i] = sbox_lazy(s[i]);
+      for (int i = RATE; i < W; i += 2) sbox_lazy2(s[i], s[i + 1]);
     }
     mds_layer_d(s, (r + 1) * W);
   }
 #pragma unroll
-  for (int k = 0; k < W; k++) s[k] = sbox_lazy(s[k]);  // the last full round before the partial rounds
+  for (int k = 0; k < W; k += 2) sbox_lazy2(s[k], s[k + 1]);  // the last full round before the partial rounds
   if (!partial_rounds(s, SameInput(), stop)) return false;
   // a form that drops outputs has its last round apart from the loop (its layer is another one); OUT_ALL keeps the loop whole
   constexpr int LOOPED = OUT == OUT_ALL ? ROUNDS : ROUNDS - 1;
@@ -597,7 +617,7 @@ GL_HD bool permute_until(uint64_t (&s)[W], Stop stop) {
   for (int r = HALF_FULL + PARTIAL; r < LOOPED; r++) {
     if (stop()) return false;
 #pragma unroll
-    for (int i = 0; i < W; i++) s[i] = sbox_lazy(s[i]);
+    for (int i = 0; i < W; i += 2) sbox_lazy2(s[i], s[i + 1]);
     mds_layer_d(s, r + 1 < ROUNDS ? (r + 1) * W : -1);
   }
   if (OUT == OUT_ALL) {
@@ -606,7 +626,7 @@ GL_HD bool permute_until(uint64_t (&s)[W], Stop stop) {
   } else {
     if (stop()) return false;
 #pragma unroll
-    for (int i = 0; i < W; i++) s[i] = sbox_lazy(s[i]);
+    for (int i = 0; i < W; i += 2) sbox_lazy2(s[i], s[i + 1]);
     mds_last_layer_d<OUT == OUT_DIGEST>(s);
   }
   return true;

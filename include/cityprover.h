@@ -156,6 +156,10 @@ int cp_lde_dev(cp_ctx *ctx, const uint64_t *coeffs_dev, size_t in_stride, int lo
  * out; a, b: ANY u64 (the kernels carry values lazily), host pointers. No call site in the reference — this is the
  * built-in self-test hook for the one arithmetic primitive every kernel shares (plonky2 `GoldilocksField::mul`). */
 int cp_field_mul(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, uint64_t *out_host, size_t count);
+/* The same for the paired product (csrc/gl.h `mul_lazy2`, what the Poseidon S-boxes are built from): one lane computes
+ * out_ab[i] = a[i] * b[i] and out_cd[i] = c[i] * d[i] together, canonical out; any u64 in, host pointers, count <= 2^27. */
+int cp_field_mul2(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, const uint64_t *c_host, const uint64_t *d_host,
+                  uint64_t *out_ab_host, uint64_t *out_cd_host, size_t count);
 
 /* ---- Poseidon-Goldilocks -------------------------------------------------------------
  * Replaces plonky2 `PoseidonPermutation::permute`, `PoseidonHash::{hash_no_pad, two_to_one}`
