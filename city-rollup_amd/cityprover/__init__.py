@@ -1114,10 +1114,60 @@ class Groth16Key:
                 "a_inf": flags_to_host(DeviceBuffer.view(p, pk.a_inf, (pk.n_wires + 7) // 8), pk.n_wires),
                 "b_inf": flags_to_host(DeviceBuffer.view(p, pk.b_inf, (pk.n_wires + 7) // 8), pk.n_wires)}
 
+    def save(self, path, raw=False, chunk_points=0):
+        """cp_groth16_key_save_file: the key as a file (include/cityprover.h has the layout), compressed points unless raw;
+        chunk_points: points per device pass (0: the library's default)"""
+        flags = GROTH16_KEY_FILE_RAW if raw else 0
+        self.prover._check(self.prover.lib.cp_groth16_key_save_file(self.prover.ctx, self.handle, os.fsencode(path), flags, int(chunk_points)))
+
+    @classmethod
+    def load(cls, prover, path, check_torsion=False, chunk_points=0):
+        """cp_groth16_key_load_file: a key like the one setup() returns, from a file and without the trapdoor; check_torsion
+        also holds every point of the five sets to [r]P = infinity"""
+        flags = GROTH16_KEY_LOAD_CHECK_TORSION if check_torsion else 0
+        handle = prover.lib.cp_groth16_key_load_file(prover.ctx, os.fsencode(path), flags, int(chunk_points))
+        if not handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+        return cls(prover, handle)
+
     def free(self):
         if self.handle:
             self.prover.lib.cp_groth16_key_destroy(self.handle)
             self.handle = None
+
+
+# ---- Groth16 keys as files ----
+GROTH16_KEY_FILE_VERSION = 1
+GROTH16_KEY_FILE_RAW = 1
+GROTH16_KEY_LOAD_CHECK_TORSION = 1
+
+
+class Groth16KeyFileInfo(ctypes.Structure):
+    _fields_ = [("version", ctypes.c_uint32), ("flags", ctypes.c_uint), ("log_domain", ctypes.c_int), ("n_wires", ctypes.c_size_t),
+                ("n_public", ctypes.c_size_t), ("n_private", ctypes.c_size_t), ("file_bytes", ctypes.c_size_t), ("checksum", ctypes.c_uint64)]
+
+
+ABI["cp_groth16_key_save_file"] = (ctypes.c_int, [_vp, _vp, ctypes.c_char_p, ctypes.c_uint, ctypes.c_size_t])
+ABI["cp_groth16_key_load_file"] = (_vp, [_vp, ctypes.c_char_p, ctypes.c_uint, ctypes.c_size_t])
+ABI["cp_groth16_key_file_info"] = (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(Groth16KeyFileInfo), ctypes.POINTER(Groth16Vk), _u64p, _u8p])
+
+
+def groth16_key_file_info(path, verify_checksum=True):
+    """cp_groth16_key_file_info: parse and validate a key file on the host (no GPU, no square roots). Returns a dict: the header's
+    fields, "vk" (Groth16Vk), "ic_xy" ((n_public, 12) u64) and "ic_inf" (n_public flags): what Groth16Verifier.create takes.
+    Raises on a bad file."""
+    lib = load_library()
+    info, vk = Groth16KeyFileInfo(), Groth16Vk()
+    rc = lib.cp_groth16_key_file_info(os.fsencode(path), int(bool(verify_checksum)), ctypes.byref(info), ctypes.byref(vk), None, None)
+    if rc != 0:
+        raise CityProverError(f"[{rc}] " + lib.cp_last_error(None).decode())
+    xy, inf = np.zeros((vk.n_public, 12), np.uint64), np.zeros(vk.n_public, np.uint8)
+    rc = lib.cp_groth16_key_file_info(os.fsencode(path), 0, None, None, _ptr(xy), inf.ctypes.data_as(_u8p))
+    if rc != 0:
+        raise CityProverError(f"[{rc}] " + lib.cp_last_error(None).decode())
+    out = {name: getattr(info, name) for name, _ in Groth16KeyFileInfo._fields_}
+    out.update(vk=vk, ic_xy=xy, ic_inf=inf)
+    return out
 
 
 # ---- pairing products and the Groth16 verifier (GT values are e(P, Q)^3: include/cityprover.h) ----

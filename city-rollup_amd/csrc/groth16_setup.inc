@@ -6,24 +6,10 @@
 //   u_i, v_i, w_i = (A^T L)_i, ...    r1cs_eval of the system transposed on the host, with L as its witness
 //   k_i, ic_i, z_j                    two element-wise kernels (groth16_setup.h)
 //   the five point sets               fixed_base_run (fixed_base.inc) over the standard generators
-// Included by bls.hip after fixed_base.inc and r1cs.inc.
-struct cp_groth16_key {
-  explicit cp_groth16_key(int dev) : device(dev), mem(dev_pool(), dev) {}
-  const int device;
-  cp_groth16_pk pk{};
-  cp_groth16_vk vk{};
-  std::vector<uint64_t> ic_xy;  // n_public x 12
-  std::vector<uint8_t> ic_inf;
-  DevBag mem;  // the five point sets and the two flag arrays
-};
+// Included by bls.hip after fixed_base.inc and r1cs.inc. The handle itself is groth16_key.h: key files make one too.
+#include "groth16_key.h"
 
 namespace {
-
-void groth16_key_free(cp_groth16_key *k) {
-  if (!k) return;
-  if (k->mem.size()) (void)hipSetDevice(k->device);
-  delete k;
-}
 
 int trapdoor_scalar(cp_ctx *ctx, const uint64_t s[4], const char *name, blsfr::Fr *out) {
   if (!(s[0] | s[1] | s[2] | s[3])) return set_error(ctx, CP_ERR_INVALID_ARG, "trapdoor: %s is zero", name);

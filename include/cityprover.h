@@ -1043,6 +1043,49 @@ int cp_groth16_verify_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, c
                                     const uint64_t *public_inputs_host, size_t n_proofs, unsigned flags,
                                     uint8_t *verdict_out_host);
 
+/* ---- Groth16 keys as files: save once after the setup, load without the trapdoor ----
+ * The reference reads its keys from a keystore directory before the first wrap (`gnark_plonky2_wrapper::initialize`,
+ * city_rollup_core_worker/src/lib.rs:37-38 and :121-122); a worker that restarts must not need the five trapdoor scalars to
+ * get its key back. The counterpart of cp_circuit_save_file / cp_circuit_load_file / cp_circuit_file_info for keys.
+ * The file is little-endian u64 words (INTEGRATION.md section 4c-4 has the table): a header, the six single points, the IC
+ * points - all affine canonical - and the five point sets in the order a_g1, b_g1, b_g2, k_g1, z_g1. A point of the sets is a
+ * compressed element (48 bytes for G1, 96 for G2: the encoding of the stored proof form above, 0x40 alone for infinity) or,
+ * with CP_GROTH16_KEY_FILE_RAW, its affine canonical coordinates (96 / 192 bytes, all zero for infinity). The points are
+ * compressed and decompressed on the device, one lane per point, in passes of chunk_points points (0: 2^16) through one
+ * staging buffer on the device and two page-locked ones on the host, so the memory beyond the key itself is bounded by
+ * chunk_points whatever the key's size. The checksum (word 2) is checked before any point is looked at.
+ *
+ * save: writes a temporary file beside `path` and renames it; a failed save leaves nothing under `path` and a file that was
+ * there before untouched. load: the key is like the one the setup returns - on the context's device, usable by any context of
+ * it, destroyed with cp_groth16_key_destroy (also after its context) - and its device arrays are byte for byte those of the
+ * key that was saved, the flag arrays and the entries under an infinity flag (the generator) included. Every point is
+ * checked to be one (x < p and a root exists, or the curve equation for raw points); CP_GROTH16_KEY_LOAD_CHECK_TORSION adds
+ * [r]P = infinity for every point of the five sets. The first refused point is named: set, index, reason.
+ * file_info: needs no context and no GPU and takes no square root: structure, version, sizes, the exact length, the header's
+ * and the IC's coordinates being canonical and, with verify_checksum != 0, the checksum. It hands out the verifying key as
+ * cp_groth16_key_vk does (ic_xy_out: n_public x 12 u64, ic_inf_out: n_public flags; any out pointer may be NULL), so a
+ * process that only verifies never reads the point sets.
+ * The structure is named by its tag (`struct cp_groth16_key_file_info`): C has one name space for functions and typedefs.
+ * Refusals - a status, or NULL, plus cp_last_error - leave the context usable and nothing allocated: CP_ERR_INVALID_ARG for a
+ * NULL argument, unknown flag bits, a key of another device, a file that cannot be opened or created (with errno's text) or
+ * that is not a well-formed key file; CP_ERR_UNSUPPORTED for another version; CP_ERR_INTERNAL for a read, write or rename that
+ * fails midway (with errno's text); CP_ERR_OOM for a refused allocation. */
+#define CP_GROTH16_KEY_FILE_VERSION 1
+#define CP_GROTH16_KEY_FILE_RAW 1u           /* save: points as affine canonical coordinates instead of compressed */
+#define CP_GROTH16_KEY_LOAD_CHECK_TORSION 1u /* load: also [r]P = infinity for every point of the five sets */
+struct cp_groth16_key_file_info {
+  uint32_t version;
+  unsigned flags;
+  int log_domain;
+  size_t n_wires, n_public, n_private;
+  size_t file_bytes;
+  uint64_t checksum;
+};
+int cp_groth16_key_save_file(cp_ctx *ctx, const cp_groth16_key *key, const char *path, unsigned flags, size_t chunk_points);
+cp_groth16_key *cp_groth16_key_load_file(cp_ctx *ctx, const char *path, unsigned flags, size_t chunk_points);
+int cp_groth16_key_file_info(const char *path, int verify_checksum, struct cp_groth16_key_file_info *info_out,
+                             cp_groth16_vk *vk_out, uint64_t *ic_xy_out, uint8_t *ic_inf_out);
+
 #ifdef __cplusplus
 }
 #endif
