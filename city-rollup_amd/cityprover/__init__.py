@@ -55,6 +55,7 @@ ABI = {
     "cp_poseidon_permute_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t]),
     "cp_field_mul": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, ctypes.c_size_t]),
     "cp_field_mul2": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, ctypes.c_size_t]),
+    "cp_field_reduce2": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, ctypes.c_size_t]),
     "cp_poseidon_permute": (ctypes.c_int, [_vp, _u64p, ctypes.c_size_t]),
     "cp_hash_no_pad": (ctypes.c_int, [_vp, _u64p, ctypes.c_size_t, ctypes.c_size_t, _u64p]),
     "cp_two_to_one": (ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_size_t, _u64p]),
@@ -300,6 +301,14 @@ class Prover:
         out_ab, out_cd = np.zeros(v[0].size, np.uint64), np.zeros(v[0].size, np.uint64)
         self._check(self.lib.cp_field_mul2(self.ctx, _ptr(v[0]), _ptr(v[1]), _ptr(v[2]), _ptr(v[3]), _ptr(out_ab), _ptr(out_cd), v[0].size))
         return out_ab, out_cd
+
+    def field_reduce2(self, lo_a, hi_a, lo_b, hi_b):
+        """(lo_a + hi_a 2^64, lo_b + hi_b 2^64) mod p element-wise with the device's paired reduction (one lane reduces both); any words in."""
+        v = [_as_u64(x).ravel().copy() for x in (lo_a, hi_a, lo_b, hi_b)]
+        assert all(x.size == v[0].size for x in v)
+        out_a, out_b = np.zeros(v[0].size, np.uint64), np.zeros(v[0].size, np.uint64)
+        self._check(self.lib.cp_field_reduce2(self.ctx, _ptr(v[0]), _ptr(v[1]), _ptr(v[2]), _ptr(v[3]), _ptr(out_a), _ptr(out_b), v[0].size))
+        return out_a, out_b
 
     def poseidon_permute(self, states):
         s = _as_u64(states).copy()

@@ -815,6 +815,37 @@ int cp_field_mul2(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, c
   return cp_d2h(ctx, out_cd_host, o1, bytes);
 } CP_CATCH(ctx)
 
+// the paired reduction (gl::reduce128_lazy2): one lane reduces lo_a + hi_a 2^64 and lo_b + hi_b 2^64 together
+__global__ __launch_bounds__(256) void k_field_reduce2(const uint64_t *__restrict__ lo_a, const uint64_t *__restrict__ hi_a,
+                                                       const uint64_t *__restrict__ lo_b, const uint64_t *__restrict__ hi_b,
+                                                       uint64_t *__restrict__ out_a, uint64_t *__restrict__ out_b, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    uint64_t r0, r1;
+    gl::reduce128_lazy2(lo_a[i], hi_a[i], lo_b[i], hi_b[i], r0, r1);
+    out_a[i] = gl::canon(r0);
+    out_b[i] = gl::canon(r1);
+  }
+}
+
+int cp_field_reduce2(cp_ctx *ctx, const uint64_t *lo_a_host, const uint64_t *hi_a_host, const uint64_t *lo_b_host, const uint64_t *hi_b_host,
+                     uint64_t *out_a_host, uint64_t *out_b_host, size_t count) try {
+  CHECK_CTX(ctx);
+  if (count == 0) return CP_OK;
+  if (!lo_a_host || !hi_a_host || !lo_b_host || !hi_b_host || !out_a_host || !out_b_host) return set_error(ctx, CP_ERR_INVALID_ARG, "NULL pointer");
+  if (count > ((size_t)1 << 27)) return set_error(ctx, CP_ERR_INVALID_ARG, "count too large");
+  const size_t bytes = count * sizeof(uint64_t);
+  CP_TRY(ensure_scratch(ctx, 6 * bytes));
+  uint64_t *la = ctx->scratch.get<uint64_t>(), *ha = la + count, *lb = ha + count, *hb = lb + count, *o0 = hb + count, *o1 = o0 + count;
+  CP_TRY(cp_h2d(ctx, la, lo_a_host, bytes));
+  CP_TRY(cp_h2d(ctx, ha, hi_a_host, bytes));
+  CP_TRY(cp_h2d(ctx, lb, lo_b_host, bytes));
+  CP_TRY(cp_h2d(ctx, hb, hi_b_host, bytes));
+  LAUNCH(ctx, "field_reduce2", k_field_reduce2, dim3(blocks_for(count, 256)), dim3(256), la, ha, lb, hb, o0, o1, count);
+  CP_TRY(cp_d2h(ctx, out_a_host, o0, bytes));
+  return cp_d2h(ctx, out_b_host, o1, bytes);
+} CP_CATCH(ctx)
+
 // ---- Poseidon -------------------------------------------------------------------------------
 
 int cp_poseidon_permute_dev(cp_ctx *ctx, uint64_t *states, size_t count) try {

@@ -270,6 +270,70 @@ GL_HD void mul_lazy2(uint64_t a0, uint64_t b0, uint64_t a1, uint64_t b1, uint64_
   r1 = mul_lazy(a1, b1);
 #endif
 }
+// Two independent 128-bit values in one go: r0 == lo0 + hi0 2^64, r1 == lo1 + hi1 2^64, each the lazy word of the two-operand
+// `reduce128_lazy`, bit for bit. It is the reduction of `mul_lazy2` without the carry-ins, for callers whose 128-bit values are no
+// products (ntt16.h's shifts): the two borrow chains alternate, so that each low-word borrow has its sibling's subtract as the first of its
+// two wait states and an `s_nop 0` as the second; the 64-bit borrow masks are ORed on the scalar side and tested ONCE, both chains are
+// repaired behind that single wave-uniform branch, and the folds run against each other exactly as in `mul_lazy2`. Per pair: one branch
+// instead of two, 2 wait states of `s_nop` (2 more behind the rare branch) instead of 8.
+GL_HD void reduce128_lazy2(uint64_t lo0, uint64_t hi0, uint64_t lo1, uint64_t hi1, uint64_t &r0, uint64_t &r1) {
+#if GL_DEVICE_ASM
+  // the borrow chains lo - hi32(hi). Wait states:
+  //   low-word borrow of A (%4): written by the 1st subtract, read by the 3rd: the 2nd subtract (chain B) + `s_nop 0`;
+  //   low-word borrow of B (%5): written by the 2nd subtract, read by the 4th: `s_nop 0` + the 3rd subtract (chain A);
+  //   the 64-bit borrows are read next by `s_or_b64` (SALU: no wait states) and, behind the branch, by the repair below.
+  uint32_t tlA, thA, tlB, thB;
+  uint64_t bA, bB, bm;
+  asm("v_sub_co_u32_e64 %0, %4, %7, %8\n\t"
+      "v_sub_co_u32_e64 %2, %5, %10, %11\n\t"
+      "s_nop 0\n\t"
+      "v_subbrev_co_u32_e64 %1, %4, 0, %9, %4\n\t"
+      "v_subbrev_co_u32_e64 %3, %5, 0, %12, %5\n\t"
+      "s_or_b64 %6, %4, %5"
+      : "=&v"(tlA), "=&v"(thA), "=&v"(tlB), "=&v"(thB), "=&s"(bA), "=&s"(bB), "=&s"(bm)
+      : "v"(lo32(lo0)), "v"(hi32(hi0)), "v"(hi32(lo0)), "v"(lo32(lo1)), "v"(hi32(hi1)), "v"(hi32(lo1))
+      : "scc");
+  uint64_t tA = pack(tlA, thA), tB = pack(tlB, thB);
+  if (__builtin_expect(bm != 0, 0)) {  // lo < hi32(hi) in either chain; a chain whose mask is zero subtracts 0
+    uint32_t nA, nB;
+    // bA, bB were written in another statement: the whole pad in front
+    asm volatile("s_nop 1\n\tv_cndmask_b32 %0, 0, -1, %2\n\tv_cndmask_b32 %1, 0, -1, %3" : "=&v"(nA), "=v"(nB) : "s"(bA), "s"(bB));
+    tA -= nA;
+    tB -= nB;
+  }
+  // the folds t0 + w2 (2^32 - 1), as in `mul_lazy2`: chain A's repair is the 64-bit add of `fold_top`, chain B's one more multiply-add,
+  // bit (0 / 1) times 2^32 - 1 plus the sum — the same value. Wait states of the carry-outs:
+  //   A (%1): written by the 1st multiply-add, read by the 1st select: the 2nd multiply-add (chain B) + `s_nop 0`;
+  //   B (%4): written by the 2nd multiply-add, read by the 2nd select: `s_nop 0` + the 1st select (chain A).
+  uint64_t fA, fB, cA, cB, cD;
+  uint32_t mA, nB;
+  asm("v_mad_u64_u32 %0, %1, %8, -1, %9\n\t"
+      "v_mad_u64_u32 %3, %4, %10, -1, %11\n\t"
+      "s_nop 0\n\t"
+      "v_cndmask_b32 %2, 0, -1, %1\n\t"
+      "v_cndmask_b32 %5, 0, 1, %4\n\t"
+      "v_mad_u64_u32 %6, %7, %5, -1, %3"
+      : "=&v"(fA), "=&s"(cA), "=&v"(mA), "=&v"(fB), "=&s"(cB), "=&v"(nB), "=&v"(r1), "=&s"(cD)
+      : "v"(lo32(hi0)), "v"(tA), "v"(lo32(hi1)), "v"(tB));
+  r0 = fA + mA;  // neither can wrap again (note (4) above `fold_top`)
+#else
+  r0 = reduce128_lazy(lo0, hi0);
+  r1 = reduce128_lazy(lo1, hi1);
+#endif
+}
+// the canonical forms of the two pairs
+GL_HD void reduce128_2(uint64_t lo0, uint64_t hi0, uint64_t lo1, uint64_t hi1, uint64_t &r0, uint64_t &r1) {
+  uint64_t t0, t1;
+  reduce128_lazy2(lo0, hi0, lo1, hi1, t0, t1);
+  r0 = canon(t0);
+  r1 = canon(t1);
+}
+GL_HD void mul2(uint64_t a0, uint64_t b0, uint64_t a1, uint64_t b1, uint64_t &r0, uint64_t &r1) {
+  uint64_t t0, t1;
+  mul_lazy2(a0, b0, a1, b1, t0, t1);
+  r0 = canon(t0);
+  r1 = canon(t1);
+}
 GL_HD uint64_t mul(uint64_t a, uint64_t b) {
   uint64_t lo, hi;
   carry_t cy;

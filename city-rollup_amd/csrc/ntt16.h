@@ -71,6 +71,138 @@ GL_HD void stage(uint64_t (&x)[16], uint64_t T) {
   }
 }
 
+// ---- the same arithmetic with independent chains issued in PAIRS -----------------------------------------------------------------
+// A lone `gl::mul` is three basic blocks and three `s_nop 1`, a lone `mul_pow2` two and a branch; with between one and two waves of a
+// SIMD ready to issue, those wait states are the wave's own. The passes below hand two independent chains at a time to
+// `gl::mul_lazy2` / `gl::reduce128_lazy2` (one branch, the siblings' instructions as wait states): the same field elements, bit for
+// bit, in the same number of VALU instructions. NTT16_SINGLE_CHAINS restores the one-chain forms for the A/B (and
+// NTT16_STAGE_TWIDDLES, the older A/B, implies them).
+#if defined(NTT16_SINGLE_CHAINS) || defined(NTT16_STAGE_TWIDDLES)
+#define NTT16_PAIRS 0
+#else
+#define NTT16_PAIRS 1
+#endif
+
+// x <- x 2^K0, y <- y 2^K1, both shifts in the same form of `mul_pow2` (both below 64, or both from 64 on)
+template <int K0, int K1>
+GL_HD void mul_pow2_2(uint64_t &x, uint64_t &y) {
+  static_assert(K0 > 0 && K0 < 96 && K1 > 0 && K1 < 96 && (K0 < 64) == (K1 < 64), "two shifts of one form");
+  if constexpr (K0 < 64) {
+    gl::reduce128_2(x << K0, x >> (64 - K0), y << K1, y >> (64 - K1), x, y);
+  } else {
+    constexpr int J0 = K0 - 64, J1 = K1 - 64;
+    const uint64_t x0 = J0 ? (x << J0) : x, x1 = J0 ? (x >> (64 - J0)) : 0;
+    const uint64_t y0 = J1 ? (y << J1) : y, y1 = J1 ? (y >> (64 - J1)) : 0;
+    uint64_t t, u;
+    gl::reduce128_2(0, x0, 0, y0, t, u);
+    x = gl::sub(t, x1 << 32);
+    y = gl::sub(u, y1 << 32);
+  }
+}
+
+// omega_16^E = +-2^K: the shift in [0, 192), 2^96 == -1
+template <bool INV>
+constexpr int w16_shift(int E) { return ((INV ? 36 : 156) * (E & 15)) % 192; }
+
+// Which differences of the stage at field bit B are shifted together: registers a[i], b[i] (b[i] < 0: a lone one), in register order,
+// a shift pairing with the next one of its form.
+struct ShiftPlan {
+  int a[8], b[8], n;
+};
+template <bool INV, int B>
+constexpr ShiftPlan shift_plan() {
+  ShiftPlan p{};
+  int pend[2] = {-1, -1};
+  for (int m = 0; m < 16; m++) {
+    if (m & (1 << B)) continue;
+    const int K = w16_shift<INV>((m & ((1 << B) - 1)) << (3 - B)) % 96;
+    if (K == 0) continue;
+    const int form = K >= 64, reg = m + (1 << B);
+    if (pend[form] < 0) {
+      pend[form] = reg;
+    } else {
+      p.a[p.n] = pend[form];
+      p.b[p.n++] = reg;
+      pend[form] = -1;
+    }
+  }
+  for (int form = 0; form < 2; form++)
+    if (pend[form] >= 0) {
+      p.a[p.n] = pend[form];
+      p.b[p.n++] = -1;
+    }
+  return p;
+}
+// the shift of the difference held in register `reg` (bit B set)
+template <bool INV, int B>
+constexpr int reg_shift(int reg) { return w16_shift<INV>((reg & ((1 << B) - 1)) << (3 - B)) % 96; }
+
+template <bool INV, int B, int I = 0>
+GL_HD void apply_shifts(uint64_t (&x)[16]) {
+  constexpr ShiftPlan p = shift_plan<INV, B>();
+  if constexpr (I < p.n) {
+    constexpr int ra = p.a[I], rb = p.b[I];
+    if constexpr (rb < 0) x[ra] = mul_pow2<reg_shift<INV, B>(ra)>(x[ra]);
+    else mul_pow2_2<reg_shift<INV, B>(ra), reg_shift<INV, B>(rb)>(x[ra], x[rb]);
+    apply_shifts<INV, B, I + 1>(x);
+  }
+}
+
+// `stage<INV, B, true>` with its non-trivial shifts two at a time: all sums and signed differences first, then the shifts
+template <bool INV, int B>
+GL_HD void stage_pairs(uint64_t (&x)[16]) {
+#pragma unroll
+  for (int m = 0; m < 16; m++) {
+    if (m & (1 << B)) continue;
+    const bool neg = w16_shift<INV>((m & ((1 << B) - 1)) << (3 - B)) >= 96;
+    const uint64_t u = x[m], v = x[m + (1 << B)];
+    x[m] = gl::add(u, v);
+    x[m + (1 << B)] = neg ? gl::sub(v, u) : gl::sub(u, v);
+  }
+  apply_shifts<INV, B>(x);
+}
+
+// e(m) of `round16`, and the K-th register (in register order) whose e(m) is E
+constexpr int round_exp(int NSTAGES, int m) {
+  int em = 0;  // bit B of m (B = 3 .. 4 - NSTAGES) weighs 2^(3 - B)
+  for (int B = 3; B >= 4 - NSTAGES; B--) em += ((m >> B) & 1) << (3 - B);
+  return em;
+}
+constexpr int round_reg(int NSTAGES, int E, int K) {
+  for (int m = 0; m < 16; m++)
+    if (round_exp(NSTAGES, m) == E && K-- == 0) return m;
+  return -1;
+}
+// registers K, K + 1, ... of exponent E times pw, two at a time; an odd one out stays single
+template <int NSTAGES, int E, int K>
+GL_HD void apply_power(uint64_t (&x)[16], uint64_t pw) {
+  constexpr int CNT = 16 >> NSTAGES;
+  if constexpr (K + 1 < CNT) {
+    constexpr int m0 = round_reg(NSTAGES, E, K), m1 = round_reg(NSTAGES, E, K + 1);
+    gl::mul2(x[m0], pw, x[m1], pw, x[m0], x[m1]);
+    apply_power<NSTAGES, E, K + 2>(x, pw);
+  } else if constexpr (K < CNT) {
+    constexpr int m0 = round_reg(NSTAGES, E, K);
+    x[m0] = gl::mul(x[m0], pw);
+  }
+}
+// The walk of `round16`: pw = T3^E. The step to T3^(E + 1) and the first application of T3^E read the same pw and form a pair; what is
+// left of this exponent's applications pairs among itself. 14 + 15 products for four stages, as in the one-chain walk.
+template <int NSTAGES, int E = 1>
+GL_HD void walk_powers(uint64_t (&x)[16], uint64_t pw, uint64_t T3) {
+  constexpr int LAST = (1 << NSTAGES) - 1;
+  if constexpr (E < LAST) {
+    constexpr int m0 = round_reg(NSTAGES, E, 0);
+    uint64_t next, r;
+    gl::mul_lazy2(pw, T3, x[m0], pw, next, r);
+    x[m0] = gl::canon(r);
+    apply_power<NSTAGES, E, 1>(x, pw);
+    walk_powers<NSTAGES, E + 1>(x, next, T3);
+  } else {
+    apply_power<NSTAGES, E, 0>(x, pw);
+  }
+}
+
 // NSTAGES DIF stages on the top bits of the 4-bit register field. T3 = omega_{2^(f+4)}^(r_lo).
 // The thread-uniform factor of stage B is T_B = T3^(2^(3-B)), and it multiplies ALL the differences of its stage: every later butterfly
 // pairs two values that carry the same T_B, so the factor commutes with the rest of the round. The stages therefore run with their
@@ -93,6 +225,12 @@ GL_HD void round16(uint64_t (&x)[16], uint64_t T3) {
       stage<INV, 0, UNIT_T>(x, T0);
     }
   }
+#elif NTT16_PAIRS
+  stage_pairs<INV, 3>(x);
+  if constexpr (NSTAGES >= 2) stage_pairs<INV, 2>(x);
+  if constexpr (NSTAGES >= 3) stage_pairs<INV, 1>(x);
+  if constexpr (NSTAGES >= 4) stage_pairs<INV, 0>(x);
+  if constexpr (!UNIT_T) walk_powers<NSTAGES>(x, T3, T3);
 #else
   stage<INV, 3, true>(x, 1);
   if constexpr (NSTAGES >= 2) stage<INV, 2, true>(x, 1);
@@ -194,6 +332,7 @@ __global__ __launch_bounds__(THREADS, (HALF && !(L == 4 && !ROWS)) ? NTT16_MIN_W
     // ROWS: the tile is contiguous — a wave-uniform base and a 32-bit position instead of a 64-bit index per element
     const uint64_t *in_t = ROWS ? in + ((size_t)blockIdx.x << LOG_TILE) : in;
     const uint64_t *ptab_t = (ROWS && ptab) ? ptab + ((size_t)blockIdx.x << LOG_TILE) : ptab;
+#if !NTT16_PAIRS
 #pragma unroll
     for (int m = 0; m < 16; m++) {
       const size_t idx = gidx<L, C, ROWS>(P + (m << F), blockIdx.x, q);
@@ -202,6 +341,18 @@ __global__ __launch_bounds__(THREADS, (HALF && !(L == 4 && !ROWS)) ? NTT16_MIN_W
       else if (a.coset_pre && a.first) v = gl::mul(v, ntt::pow_table(a.stab, idx));
       x[m] = v;
     }
+#else
+#pragma unroll
+    for (int m = 0; m < 16; m += 2) {  // the products on load, two registers at a time
+      const int p0 = P + (m << F), p1 = P + ((m + 1) << F);
+      const size_t idx0 = gidx<L, C, ROWS>(p0, blockIdx.x, q), idx1 = gidx<L, C, ROWS>(p1, blockIdx.x, q);
+      uint64_t v0 = ROWS ? in_t[p0] : in[idx0], v1 = ROWS ? in_t[p1] : in[idx1];
+      if (ptab) gl::mul2(v0, ROWS ? ptab_t[p0] : ptab[idx0], v1, ROWS ? ptab_t[p1] : ptab[idx1], v0, v1);
+      else if (a.coset_pre && a.first) gl::mul2(v0, ntt::pow_table(a.stab, idx0), v1, ntt::pow_table(a.stab, idx1), v0, v1);
+      x[m] = v0;
+      x[m + 1] = v1;
+    }
+#endif
     if constexpr (f == 0) {
       round16<INV, B0, true>(x, 1);
     } else {
@@ -252,14 +403,30 @@ __global__ __launch_bounds__(THREADS, (HALF && !(L == 4 && !ROWS)) ? NTT16_MIN_W
 #pragma unroll
         for (int j = 0; j < 16; j++) {
           const int m = ((j & 1) << 3) | ((j & 2) << 1) | ((j & 4) >> 1) | ((j & 8) >> 3);
+#if NTT16_PAIRS
+          if (j < 15) {  // the application and the walk step read the same w: a pair
+            uint64_t r, next;
+            gl::mul_lazy2(x[m], w, w, G, r, next);
+            x[m] = gl::canon(r);
+            w = next;
+          } else {
+            x[m] = gl::mul(x[m], w);
+          }
+#else
           x[m] = gl::mul(x[m], w);
           if (j < 15) w = gl::mul_lazy(w, G);  // the running power stays lazy: a product takes any u64
+#endif
         }
       }
     }
     if (a.last && a.scale) {
+#if NTT16_PAIRS
+#pragma unroll
+      for (int m = 0; m < 16; m += 2) gl::mul2(x[m], a.scale, x[m + 1], a.scale, x[m], x[m + 1]);
+#else
 #pragma unroll
       for (int m = 0; m < 16; m++) x[m] = gl::mul(x[m], a.scale);
+#endif
     }
     if (ROWS && a.natural_out) {
       // single-pass transform: position r holds X[rev_L(r)]; un-permute through LDS (HALF: low words, then high words), store coalesced

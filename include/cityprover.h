@@ -160,6 +160,11 @@ int cp_field_mul(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, ui
  * out_ab[i] = a[i] * b[i] and out_cd[i] = c[i] * d[i] together, canonical out; any u64 in, host pointers, count <= 2^27. */
 int cp_field_mul2(cp_ctx *ctx, const uint64_t *a_host, const uint64_t *b_host, const uint64_t *c_host, const uint64_t *d_host,
                   uint64_t *out_ab_host, uint64_t *out_cd_host, size_t count);
+/* The paired reduction (csrc/gl.h `reduce128_lazy2`, what the shift twiddles of the radix-16 NTT passes go through): one lane
+ * reduces out_a[i] = lo_a[i] + hi_a[i] 2^64 and out_b[i] = lo_b[i] + hi_b[i] 2^64 mod p together, canonical out; any words in,
+ * host pointers, count <= 2^27. */
+int cp_field_reduce2(cp_ctx *ctx, const uint64_t *lo_a_host, const uint64_t *hi_a_host, const uint64_t *lo_b_host,
+                     const uint64_t *hi_b_host, uint64_t *out_a_host, uint64_t *out_b_host, size_t count);
 
 /* ---- Poseidon-Goldilocks -------------------------------------------------------------
  * Replaces plonky2 `PoseidonPermutation::permute`, `PoseidonHash::{hash_no_pad, two_to_one}`
