@@ -1260,6 +1260,29 @@ class Groth16Verifier:
                                                        out.ctypes.data_as(_u8p)))
         return out
 
+    def _verify_all(self, fn, proofs, n, weights, publics, flags, prover):
+        p = prover or self.prover
+        pub = None
+        if self.n_public > 1:
+            pub = _as_u64(publics).reshape(n, self.n_public - 1, 4)
+        w = _weights128(weights, n)
+        out, path = np.zeros(n, np.uint8), ctypes.c_int(-1)
+        p._check(getattr(p.lib, fn)(p.ctx, self.handle, proofs, None if pub is None else _ptr(pub), n, _ptr(w), flags, out.ctypes.data_as(_u8p),
+                                    ctypes.byref(path)))
+        return out, path.value
+
+    def verify_all(self, proofs, weights, publics=None, flags=0, prover=None):
+        """verify() under one final exponentiation (cp_groth16_verify_all_bls12381). weights: one non-zero 128-bit value per proof,
+        as n ints or an (n, 2) u64 array; they must be unpredictable to whoever made the proofs (e.g. secrets.randbits(128)).
+        Returns (verdicts, path): path 0 when the aggregated equation held, 1 when the per-proof check had to decide."""
+        proofs = _as_u64(proofs).reshape(-1, 48)
+        return self._verify_all("cp_groth16_verify_all_bls12381", _ptr(proofs), len(proofs), weights, publics, flags, prover)
+
+    def verify_all_city(self, blobs, weights, publics=None, flags=0, prover=None):
+        """verify_all() with the proofs as stored (cp_groth16_verify_all_city_bls12381)"""
+        blobs = _city_blobs(blobs)
+        return self._verify_all("cp_groth16_verify_all_city_bls12381", blobs.ctypes.data_as(_u8p), len(blobs), weights, publics, flags, prover)
+
     def close(self):
         if self.handle:
             self.prover.lib.cp_groth16_verifier_destroy(self.handle)
@@ -1268,6 +1291,18 @@ class Groth16Verifier:
 
 ABI["cp_groth16_proofs_unpack_city_bls12381"] = (ctypes.c_int, [_vp, _u8p, ctypes.c_size_t, _u64p, _u8p])
 ABI["cp_groth16_verify_city_bls12381"] = (ctypes.c_int, [_vp, _vp, _u8p, _u64p, ctypes.c_size_t, ctypes.c_uint, _u8p])
+ABI["cp_groth16_verify_all_bls12381"] = (ctypes.c_int, [_vp, _vp, _u64p, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint, _u8p, ctypes.POINTER(ctypes.c_int)])
+ABI["cp_groth16_verify_all_city_bls12381"] = (ctypes.c_int, [_vp, _vp, _u8p, _u64p, ctypes.c_size_t, _u64p, ctypes.c_uint, _u8p, ctypes.POINTER(ctypes.c_int)])
+
+
+def _weights128(weights, n):
+    """n ints below 2^128 or an (n, 2) u64 array -> a contiguous (n, 2) u64 array"""
+    if isinstance(weights, np.ndarray):
+        return _as_u64(weights).reshape(n, 2)
+    weights = [int(w) for w in weights]
+    if len(weights) != n or any(w < 0 or w >> 128 for w in weights):
+        raise ValueError("one weight of at most 128 bits per proof")
+    return np.array([[w & (2**64 - 1), w >> 64] for w in weights], np.uint64).reshape(n, 2)
 
 
 def _city_blobs(blobs):

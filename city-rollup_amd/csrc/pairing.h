@@ -360,6 +360,17 @@ PAIRING_FN bool in_r_torsion(const bls::AffineT<F> &p) {
   }
   return bls::jac_is_inf(t);
 }
+// ---- [k] P in G1 for a short scalar: k < 2^128 as four 32-bit words, plain double-and-add from the top bit with the group
+// law of bls12_381.h. Infinity comes out only for k = 0 or a P of small order (outside the r-torsion). ----
+PAIRING_FN bls::Jac g1_mul_u128(const bls::Affine &p, const uint32_t *k) {
+  bls::Jac t = bls::jac_inf<Fp>();
+#pragma unroll 1
+  for (int i = 127; i >= 0; i--) {
+    t = bls::jac_double(t);
+    if ((k[i >> 5] >> (i & 31)) & 1) t = bls::jac_add_mixed(t, p);
+  }
+  return t;
+}
 GL_HD bool words_below_p(const uint32_t *w) {  // 12 words < p ?
   for (int k = 11; k >= 0; k--) {
     if (w[k] < BLS_P32[k]) return true;

@@ -3,6 +3,8 @@
 // fixedbase::k_mul - and the entry points. The work is split into several kernels, none of which holds more than one of
 // the big loops: point checks, the public-input sum, the Miller loop, and the product with the final exponentiation. In front of
 // them, for proofs in their stored 192-byte form, the decompression (bls_sqrt.h): one launch for the F_p roots, one for the F_p^2 roots.
+// Beside them, for a batch under one final exponentiation: the short multiples of A, the weighted sums of the public inputs, and the
+// product tree over the Miller values; its two point sums go through the MSM's device entry point (bls.hip).
 #include "core.h"
 #include "pairing.h"
 #include "bls_sqrt.h"
@@ -131,6 +133,84 @@ __global__ __launch_bounds__(LANES) void k_final(const uint32_t *__restrict__ mi
     for (int c = 0; c < 6; c++) bls::Field<Fp2>::to_canonical(f12_get(f, c), (uint32_t *)(gt + j * CP_GT_WORDS + 12 * c));
 }
 
+// ---- the whole batch under one final exponentiation (cp_groth16_verify_all_bls12381) ----
+// One lane per proof closes the point and input checks and scales A. st_a / st_b / st_c: the point statuses of A, B, C as
+// k_points left them; st_a doubles as the Miller kernel's skip flag of pair t and is rewritten as such.
+//   pre[t]  = the verdict the checks alone give: the largest of 2 (a point status 1 or 2), 3, 4 (a public input >= r), else 0
+//   dead[t] = 1 where pre[t] != 0: the proof takes no part in the aggregated equation (the MSM's infinity flag of C_t)
+//   wide[t] = the weight as a 256-bit MSM scalar (zero where dead)
+//   a[t]    = rho_t A_t, affine, where the proof is live; st_a[t] = 1 where pair t is to contribute one (dead, or rho_t A_t is
+//             infinity: an A of small order, which only CP_PAIRING_TRUSTED lets through)
+__global__ __launch_bounds__(LANES) void k_scale_g1(bls::Affine *__restrict__ a, uint8_t *__restrict__ st_a, const uint8_t *__restrict__ st_b,
+                                                    const uint8_t *__restrict__ st_c, size_t n_public, const uint64_t *__restrict__ publics,
+                                                    const uint64_t *__restrict__ weights, size_t n, uint8_t *__restrict__ pre, uint8_t *__restrict__ dead,
+                                                    uint64_t *__restrict__ wide) {
+  const size_t t = (size_t)blockIdx.x * LANES + threadIdx.x;
+  if (t >= n) return;
+  int v = 0;
+  const int st[3] = {st_a[t], st_b[t], st_c[t]};
+  for (int k = 0; k < 3; k++) {
+    const int c = st[k] == 1 ? 2 : st[k];
+    v = c > v ? c : v;
+  }
+  for (size_t i = 1; i < n_public; i++)
+    if (!blsfr::fr_is_canonical((const uint32_t *)(publics + (t * (n_public - 1) + (i - 1)) * 4))) v = 4;
+  const bool live = v == 0;
+  pre[t] = (uint8_t)v;
+  dead[t] = live ? 0 : 1;
+  wide[4 * t] = live ? weights[2 * t] : 0;
+  wide[4 * t + 1] = live ? weights[2 * t + 1] : 0;
+  wide[4 * t + 2] = 0;
+  wide[4 * t + 3] = 0;
+  bool skip = !live;
+  if (live) {
+    const bls::Jac m = g1_mul_u128(a[t], (const uint32_t *)(weights + 2 * t));
+    skip = bls::jac_is_inf(m);
+    if (!skip) a[t] = bls::jac_to_affine(m);
+  }
+  st_a[t] = skip ? 1 : 0;
+}
+
+// s_0 = sum_t rho_t, s_j = sum_t rho_t x_tj (j >= 1) mod r over the live proofs: workgroup j strides over t, each lane keeps
+// a running sum in Montgomery form, and the lanes' sums meet in a tree through LDS. s: n_public canonical 256-bit scalars,
+// what the MSM over the IC points reads.
+constexpr unsigned SUM_LANES = 256;
+__global__ __launch_bounds__(SUM_LANES) void k_fr_weighted_sums(const uint64_t *__restrict__ wide, const uint8_t *__restrict__ dead,
+                                                                const uint64_t *__restrict__ publics, size_t n_public, size_t n,
+                                                                uint64_t *__restrict__ s) {
+  __shared__ blsfr::Fr part[SUM_LANES];
+  const size_t j = blockIdx.x;
+  blsfr::Fr acc = blsfr::fr_zero();
+#pragma unroll 1
+  for (size_t t = threadIdx.x; t < n; t += SUM_LANES) {
+    if (dead[t]) continue;
+    blsfr::Fr term = blsfr::fr_from_canonical((const uint32_t *)(wide + 4 * t));
+    if (j) term = blsfr::fr_mul(term, blsfr::fr_from_canonical((const uint32_t *)(publics + (t * (n_public - 1) + (j - 1)) * 4)));
+    acc = blsfr::fr_add(acc, term);
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll 1
+  for (unsigned h = SUM_LANES / 2; h; h >>= 1) {
+    if (threadIdx.x < h) part[threadIdx.x] = blsfr::fr_add(part[threadIdx.x], part[threadIdx.x + h]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) blsfr::fr_to_canonical(part[0], (uint32_t *)(s + 4 * j));
+}
+
+// One round of the product tree over the m values in columns 0 .. m - 1 of `vals` ([168][stride]): lane i < m - half
+// multiplies column i by column i + half (half = ceil(m / 2)) in its LDS column and writes the product back to column i, which
+// no other lane reads in this round; with m odd, column half - 1 has no partner and stays. The host halves m until one is left.
+__global__ __launch_bounds__(LANES) void k_gt_product(uint32_t *__restrict__ vals, size_t stride, size_t m, size_t half) {
+  __shared__ uint32_t f_lds[F12_WORDS][LANES];
+  const size_t i = (size_t)blockIdx.x * LANES + threadIdx.x;
+  if (i >= m - half) return;
+  const F12 f = {&f_lds[0][threadIdx.x], LANES};
+  const F12 lo = {vals + i, stride};
+  f12_mul(f, lo, F12{vals + i + half, stride});
+  f12_copy(lo, f);
+}
+
 // ---- the stored proof form: n x 192 bytes, pi_a | pi_b_a0 | pi_b_a1 | pi_c, each a compressed point (bls_sqrt.h) ----
 // One lane per element, the F_p elements and the F_p^2 element in launches of their own: a wave never mixes the one
 // exponentiation of a G1 root with the two of a G2 root. Lane e of k_unpack_g1 takes pi_a (e even) or pi_c (e odd) of proof
@@ -166,8 +246,9 @@ struct cp_groth16_verifier {
   size_t n_public = 0;
   bls::Affine *ic = nullptr;             // n_public points, Montgomery form (a flagged entry is not read)
   uint8_t *ic_inf = nullptr;
-  bls::Affine2 *neg_gamma_delta = nullptr;  // -gamma, -delta
+  bls::Affine2 *neg_gamma_delta = nullptr;  // -gamma, -delta, -beta (the tail pairs of the aggregated equation, in this order)
   uint32_t *target = nullptr;            // e(alpha, beta)^c: 168 Montgomery limbs
+  bls::Affine alpha = {};                // on the host: the aggregated equation takes a multiple of it per call
   DevBag mem;
 };
 
@@ -331,9 +412,9 @@ int verifier_build(cp_ctx *ctx, const cp_groth16_vk *vk, const uint64_t *ic_xy, 
   const size_t np = vk->n_public;
   if (np == 0 || np > ((size_t)1 << 20)) return set_error(ctx, CP_ERR_INVALID_ARG, "verifying key: n_public %zu out of range (1 .. 2^20; it counts wire 0)", np);
   bls::Affine alpha;
-  bls::Affine2 beta, gd[2];
+  bls::Affine2 gd[3];  // gamma, delta, beta
   CP_TRY(key_point<bls::Fp>(ctx, vk->alpha_g1, "alpha_g1", (size_t)-1, &alpha));
-  CP_TRY(key_point<bls::Fp2>(ctx, vk->beta_g2, "beta_g2", (size_t)-1, &beta));
+  CP_TRY(key_point<bls::Fp2>(ctx, vk->beta_g2, "beta_g2", (size_t)-1, &gd[2]));
   CP_TRY(key_point<bls::Fp2>(ctx, vk->gamma_g2, "gamma_g2", (size_t)-1, &gd[0]));
   CP_TRY(key_point<bls::Fp2>(ctx, vk->delta_g2, "delta_g2", (size_t)-1, &gd[1]));
   for (auto &q : gd) q.y = pairing::fp2_neg(q.y);
@@ -362,14 +443,15 @@ int verifier_build(cp_ctx *ctx, const cp_groth16_vk *vk, const uint64_t *ic_xy, 
   HIP_TRY(ctx, hipMemcpyAsync(v->target, target, sizeof target, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, sync_stream(ctx));  // the host arrays die with this call
   v->n_public = np;
+  v->alpha = alpha;
   return CP_OK;
 }
 
 // proofs: n x 48 u64 of coordinates (city = false) or n x 192 bytes in the stored form (city = true), which are decompressed on
 // the device into the same staging array: a proof refused there is 48 zero words, on neither the curve nor the twist, and
 // gets verdict 2 from the point checks like any other bad point.
-int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bool city, const uint64_t *publics, size_t n, unsigned flags, uint8_t *verdict_out) {
-  using namespace pairing;
+// the refusals that both forms of the verifier share
+int verify_args(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, const uint64_t *publics, size_t n, unsigned flags, const uint8_t *verdict_out) {
   if (!v) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: the verifier is NULL");
   if (v->device != ctx->device) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: the verifier lives on device %d, the context on device %d", v->device, ctx->device);
   if (!proofs || !verdict_out) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: NULL argument");
@@ -378,6 +460,12 @@ int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bo
   if (flags & ~CP_PAIRING_TRUSTED) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: unknown flag bits 0x%x", flags);
   if (n > MAX_PAIRS / 3) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: more than 2^24 / 3 proofs in one call");
   if ((v->n_public - 1) > (((size_t)1 << 40) / n)) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: n_proofs x public inputs is too large");
+  return CP_OK;
+}
+
+int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bool city, const uint64_t *publics, size_t n, unsigned flags, uint8_t *verdict_out) {
+  using namespace pairing;
+  CP_TRY(verify_args(ctx, v, proofs, publics, n, flags, verdict_out));
   Batch b;
   b.n = n; b.k = 3; b.n_pairs = 3 * n;
   const size_t pub_words = n * (v->n_public - 1) * 4;
@@ -404,6 +492,139 @@ int verify_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bo
   CP_TRY(batch_run(ctx, b, v->target, 1));
   HIP_TRY(ctx, hipMemcpyAsync(verdict_out, b.status, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, sync_stream(ctx));
+  return CP_OK;
+}
+
+// the device arrays of one aggregated check: n pairs (rho_t A_t, B_t) and the three tail pairs behind them
+struct AllBatch {
+  size_t n = 0, n_pairs = 0;
+  uint64_t *proofs = nullptr, *publics = nullptr, *weights = nullptr, *wide = nullptr, *s = nullptr;
+  bls::Affine *g1 = nullptr, *c = nullptr;  // g1: n + 3 (A, then the tails); c: n, dense, what the MSM reads
+  bls::Affine2 *g2 = nullptr;
+  uint8_t *st1 = nullptr, *st2 = nullptr, *st_c = nullptr, *pre = nullptr, *dead = nullptr, *zero = nullptr, *status = nullptr;
+  uint32_t *miller = nullptr, *tmp = nullptr, *work = nullptr;
+  City city;
+  void carve(Carve &k, size_t pub_words, size_t n_public, bool stored) {
+    proofs = k.take<uint64_t>(n * 48 * 8);
+    publics = pub_words ? k.take<uint64_t>(pub_words * 8) : nullptr;
+    weights = k.take<uint64_t>(n * 16);
+    wide = k.take<uint64_t>(n * 32);
+    s = k.take<uint64_t>(n_public * 32);
+    g1 = k.take<bls::Affine>(n_pairs * sizeof(bls::Affine));
+    c = k.take<bls::Affine>(n * sizeof(bls::Affine));
+    g2 = k.take<bls::Affine2>(n_pairs * sizeof(bls::Affine2));
+    st1 = k.take<uint8_t>(n_pairs);
+    st2 = k.take<uint8_t>(n_pairs);
+    st_c = k.take<uint8_t>(n);
+    pre = k.take<uint8_t>(n);
+    dead = k.take<uint8_t>(n);
+    zero = k.take<uint8_t>(1);
+    status = k.take<uint8_t>(1);
+    miller = k.take<uint32_t>(n_pairs * pairing::F12_WORDS * 4);
+    tmp = k.take<uint32_t>(n_pairs * pairing::F12_WORDS * 4);
+    work = k.take<uint32_t>(4 * pairing::F12_WORDS * 4);
+    if (stored) city.carve(k, n);
+  }
+};
+
+// The aggregated equation over the proofs that pass the point and input checks (pre[t] = 0):
+//   prod_t e(rho_t A_t, B_t) . e(sum_j s_j IC_j, -gamma) . e(sum_t rho_t C_t, -delta) . e(s_0 alpha, -beta) = 1.
+// *holds: whether it does (true as well when no proof is live: nothing is left to check). pre: n bytes on the host.
+int aggregate_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bool city, const uint64_t *publics, const uint64_t *weights, size_t n,
+                  unsigned flags, uint8_t *pre, bool *holds) {
+  using namespace pairing;
+  AllBatch b;
+  b.n = n; b.n_pairs = n + 3;
+  const size_t np = v->n_public, pub_words = n * (np - 1) * 4;
+  DevBag bag = ctx->bag();
+  Carve size;
+  b.carve(size, pub_words, np, city);
+  Carve k;
+  CP_TRY(alloc_status(ctx, bag.alloc(&k.base, size.off), size.off));
+  b.carve(k, pub_words, np, city);
+  if (city) {
+    HIP_TRY(ctx, hipMemcpyAsync(b.city.bytes, proofs, n * 192, hipMemcpyHostToDevice, ctx->stream));
+    CP_TRY(city_unpack(ctx, b.city, n, b.proofs));
+  } else {
+    HIP_TRY(ctx, hipMemcpyAsync(b.proofs, proofs, n * 48 * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (pub_words) HIP_TRY(ctx, hipMemcpyAsync(b.publics, publics, pub_words * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(b.weights, weights, n * 16, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(b.st1, 0, b.n_pairs, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(b.st2, 0, b.n_pairs, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(b.zero, 0, 1, ctx->stream));
+  const int torsion = (flags & CP_PAIRING_TRUSTED) ? 0 : 1;
+  const dim3 grid(blocks_for(n, LANES)), block(LANES);
+  LAUNCH(ctx, "pairing_points_g1", k_points<Fp>, grid, block, (const uint64_t *)b.proofs, (size_t)48, (const uint8_t *)nullptr, n, torsion, b.g1, b.st1, (size_t)1, (size_t)0);
+  LAUNCH(ctx, "pairing_points_g1", k_points<Fp>, grid, block, (const uint64_t *)(b.proofs + 36), (size_t)48, (const uint8_t *)nullptr, n, torsion, b.c, b.st_c, (size_t)1, (size_t)0);
+  LAUNCH(ctx, "pairing_points_g2", k_points<Fp2>, grid, block, (const uint64_t *)(b.proofs + 12), (size_t)48, (const uint8_t *)nullptr, n, torsion, b.g2, b.st2, (size_t)1, (size_t)0);
+  LAUNCH(ctx, "groth16_scale_g1", k_scale_g1, grid, block, b.g1, b.st1, (const uint8_t *)b.st2, (const uint8_t *)b.st_c, np, (const uint64_t *)b.publics,
+         (const uint64_t *)b.weights, n, b.pre, b.dead, b.wide);
+  LAUNCH(ctx, "groth16_weighted_sums", k_fr_weighted_sums, dim3((unsigned)np), dim3(SUM_LANES), (const uint64_t *)b.wide, (const uint8_t *)b.dead,
+         (const uint64_t *)b.publics, np, n, b.s);
+  uint64_t s0[4];
+  HIP_TRY(ctx, hipMemcpyAsync(pre, b.pre, n, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(s0, b.s, sizeof s0, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, sync_stream(ctx));
+  size_t live = 0;
+  for (size_t t = 0; t < n; t++) live += pre[t] == 0;
+  *holds = true;
+  if (!live) return CP_OK;
+  // the three tail points: two sums through the MSM on the device (k_points left C in the form the MSM reads, the IC points
+  // are held in it), the multiple of alpha on the host; tail[i] pairs with entry i of the verifier's -gamma, -delta, -beta
+  uint64_t sum_xy[2][12];
+  int sum_inf[2];
+  CP_TRY(cp_msm_bls12381_g1_dev(ctx, b.s, v->ic, v->ic_inf, np, sum_xy[0], &sum_inf[0]));
+  CP_TRY(cp_msm_bls12381_g1_dev(ctx, b.wide, b.c, b.dead, n, sum_xy[1], &sum_inf[1]));
+  bls::Affine tail[3];
+  uint8_t tail_inf[3];
+  for (int i = 0; i < 2; i++) {
+    tail_inf[i] = sum_inf[i] ? 1 : 0;
+    tail[i] = bls::affine_from_canonical<Fp>((const uint32_t *)sum_xy[i]);
+  }
+  bls::Jac sa = bls::jac_inf<Fp>();
+  for (int i = 254; i >= 0; i--) {
+    sa = bls::jac_double(sa);
+    if ((s0[i >> 6] >> (i & 63)) & 1) sa = bls::jac_add_mixed(sa, v->alpha);
+  }
+  tail_inf[2] = bls::jac_is_inf(sa) ? 1 : 0;
+  tail[2] = tail_inf[2] ? bls::Affine{bls::fp_zero(), bls::fp_zero()} : bls::jac_to_affine(sa);
+  HIP_TRY(ctx, hipMemcpyAsync(b.g1 + n, tail, sizeof tail, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(b.st1 + n, tail_inf, sizeof tail_inf, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(b.g2 + n, v->neg_gamma_delta, 3 * sizeof(bls::Affine2), hipMemcpyDeviceToDevice, ctx->stream));
+  LAUNCH(ctx, "pairing_miller", k_miller, dim3(blocks_for(b.n_pairs, LANES)), block, (const bls::Affine *)b.g1, (const bls::Affine2 *)b.g2, (const uint8_t *)nullptr,
+         (const uint8_t *)nullptr, (const uint8_t *)b.st1, (const uint8_t *)b.st2, b.n_pairs, b.miller, b.tmp);
+  for (size_t m = b.n_pairs; m > 1;) {
+    const size_t half = (m + 1) / 2;
+    LAUNCH(ctx, "groth16_gt_product", k_gt_product, dim3(blocks_for(m - half, LANES)), block, b.miller, b.n_pairs, m, half);
+    m = half;
+  }
+  // one lane: the final exponentiation of column 0 and the comparison with one
+  LAUNCH(ctx, "pairing_final", k_final, dim3(1), block, (const uint32_t *)b.miller, b.n_pairs, (size_t)1, (size_t)1, b.work, (const uint32_t *)nullptr,
+         (const uint8_t *)b.zero, (const uint8_t *)b.zero, (const uint8_t *)b.zero, 1, (uint64_t *)nullptr, (uint8_t *)nullptr, b.status);
+  uint8_t status = 1;
+  HIP_TRY(ctx, hipMemcpyAsync(&status, b.status, 1, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, sync_stream(ctx));
+  *holds = status == 0;
+  return CP_OK;
+}
+
+int verify_all_run(cp_ctx *ctx, const cp_groth16_verifier *v, const void *proofs, bool city, const uint64_t *publics, size_t n, const uint64_t *weights,
+                   unsigned flags, uint8_t *verdict_out, int *path_out) {
+  CP_TRY(verify_args(ctx, v, proofs, publics, n, flags, verdict_out));
+  if (!weights) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: weights_host is NULL");
+  for (size_t t = 0; t < n; t++)
+    if (!(weights[2 * t] | weights[2 * t + 1])) return set_error(ctx, CP_ERR_INVALID_ARG, "verify: weight %zu is zero", t);
+  std::vector<uint8_t> pre(n);
+  bool holds = false;
+  CP_TRY(aggregate_run(ctx, v, proofs, city, publics, weights, n, flags, pre.data(), &holds));  // its device memory is released here
+  if (holds) {
+    memcpy(verdict_out, pre.data(), n);
+  } else {
+    // some live proof is bad: the per-proof check over the whole batch says which (and repeats the verdicts of the checks)
+    CP_TRY(verify_run(ctx, v, proofs, city, publics, n, flags, verdict_out));
+  }
+  if (path_out) *path_out = holds ? 0 : 1;
   return CP_OK;
 }
 
@@ -446,6 +667,18 @@ int cp_groth16_verify_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, c
                                     unsigned flags, uint8_t *verdict_out_host) try {
   CHECK_CTX(ctx);
   return verify_run(ctx, v, proofs_host, true, public_inputs_host, n_proofs, flags, verdict_out_host);
+} CP_CATCH(ctx)
+
+int cp_groth16_verify_all_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint64_t *proofs_host, const uint64_t *public_inputs_host, size_t n_proofs,
+                                   const uint64_t *weights_host, unsigned flags, uint8_t *verdict_out_host, int *path_out) try {
+  CHECK_CTX(ctx);
+  return verify_all_run(ctx, v, proofs_host, false, public_inputs_host, n_proofs, weights_host, flags, verdict_out_host, path_out);
+} CP_CATCH(ctx)
+
+int cp_groth16_verify_all_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint8_t *proofs_host, const uint64_t *public_inputs_host, size_t n_proofs,
+                                        const uint64_t *weights_host, unsigned flags, uint8_t *verdict_out_host, int *path_out) try {
+  CHECK_CTX(ctx);
+  return verify_all_run(ctx, v, proofs_host, true, public_inputs_host, n_proofs, weights_host, flags, verdict_out_host, path_out);
 } CP_CATCH(ctx)
 
 int cp_groth16_proofs_unpack_city_bls12381(cp_ctx *ctx, const uint8_t *proofs_host, size_t n_proofs, uint64_t *proofs_out_host, uint8_t *status_out_host) try {

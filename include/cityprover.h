@@ -1048,6 +1048,33 @@ int cp_groth16_verify_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, c
                                     const uint64_t *public_inputs_host, size_t n_proofs, unsigned flags,
                                     uint8_t *verdict_out_host);
 
+/* A batch under ONE final exponentiation: the standard batch check of Groth16. verdict_out_host has the meaning, the values
+ * and the precedence of cp_groth16_verify_bls12381, and for weights the makers of the proofs could not predict the verdicts
+ * are that function's, byte for byte. The call proceeds in four steps:
+ *  1. the per-proof point and input checks run as there (coordinates, curve and twist, the r-torsion unless
+ *     CP_PAIRING_TRUSTED is set, public inputs below r; in the _city_ form an unpack status other than 0 gives verdict 2);
+ *  2. the proofs that pass, taken together, go through the aggregated equation with the weights rho_t:
+ *       prod_t e(rho_t A_t, B_t) = e(sum_t rho_t C_t, delta) e(sum_j s_j IC_j, gamma) e(s_0 alpha, beta),
+ *       s_0 = sum_t rho_t mod r, s_j = sum_t rho_t x_tj mod r
+ *     - one Miller loop and one 128-bit multiple in G1 per proof, two MSMs, three more Miller loops and one final
+ *     exponentiation for the whole batch;
+ *  3. if it holds, those proofs get verdict 0 and *path_out is 0;
+ *  4. if it does not, cp_groth16_verify_bls12381's own check runs over the batch and fills the verdicts, and *path_out is 1:
+ *     a batch with a bad proof costs the per-proof check plus the aggregated attempt.
+ * weights_host: n_proofs x 2 u64, a 128-bit value per proof, little-endian words, not zero. The library draws no
+ * randomness, here as everywhere in this ABI: the weights are the caller's, and they MUST be unpredictable to whoever made
+ * the proofs (fresh output of a cryptographic generator, drawn after the proofs are fixed). A batch accepted under
+ * predictable weights proves nothing about its members: with equal weights, two proofs whose C are off by +D and -D pass
+ * together though each alone is rejected. path_out may be NULL.
+ * Refusals are those of cp_groth16_verify_bls12381, and CP_ERR_INVALID_ARG as well for weights_host = NULL and for a weight
+ * of zero (the message names its index). A refused allocation is CP_ERR_OOM and the context stays usable. */
+int cp_groth16_verify_all_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint64_t *proofs_host,
+                                   const uint64_t *public_inputs_host, size_t n_proofs, const uint64_t *weights_host,
+                                   unsigned flags, uint8_t *verdict_out_host, int *path_out);
+int cp_groth16_verify_all_city_bls12381(cp_ctx *ctx, const cp_groth16_verifier *v, const uint8_t *proofs_host,
+                                        const uint64_t *public_inputs_host, size_t n_proofs, const uint64_t *weights_host,
+                                        unsigned flags, uint8_t *verdict_out_host, int *path_out);
+
 /* ---- Groth16 keys as files: save once after the setup, load without the trapdoor ----
  * The reference reads its keys from a keystore directory before the first wrap (`gnark_plonky2_wrapper::initialize`,
  * city_rollup_core_worker/src/lib.rs:37-38 and :121-122); a worker that restarts must not need the five trapdoor scalars to

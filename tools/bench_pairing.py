@@ -11,7 +11,10 @@ The same for bare pairings (k = 1). Prints one JSON line and writes profiles/pai
 
 With --city, instead: the stored 192-byte form at the same batch sizes (run_city below), written to profiles/pairing_city.json.
 
-usage: bench_pairing.py [batch sizes, comma separated: default 1,64,4096,65536] [--reps N] [--city]"""
+With --all, instead: cp_groth16_verify_all_bls12381 (one final exponentiation for the batch) against the per-proof function on the
+same proofs (run_all below), and at the largest size a batch with one bad proof; written to profiles/groth16_verify_all.json.
+
+usage: bench_pairing.py [batch sizes, comma separated: default 1,64,4096,65536] [--reps N] [--city | --all]"""
 import ctypes
 import json
 import os
@@ -173,6 +176,93 @@ def main_city(sizes, reps):
     print(json.dumps(out))
 
 
+def run_all(prover, verifier, proofs, pubs, n, reps):
+    """cp_groth16_verify_all_bls12381 against cp_groth16_verify_bls12381 on the same n valid proofs, one process, the two legs
+    alternating within a repeat, with and without CP_PAIRING_TRUSTED. The ratio is all / per_proof: below 1 the aggregated path
+    wins. one_bad (asked for at the largest size): the same batch with the C of one proof swapped for its neighbour's, which
+    sends verify_all down the fallback path - the aggregated attempt, then the per-proof check."""
+    rng = np.random.default_rng(n)
+    idx = np.arange(n) % len(proofs)
+    pr, pu = np.ascontiguousarray(proofs[idx]), np.ascontiguousarray(pubs[idx])
+    w = np.frombuffer(rng.bytes(16 * n), np.uint64).reshape(n, 2) | np.uint64(1)
+    out = {"n": n, "reps": reps}
+
+    def timed(legs):
+        for f in legs.values():
+            f()                                                  # warm-up of every shape
+        walls = {k: [] for k in legs}
+        for _ in range(reps):
+            for k, f in legs.items():
+                t0 = time.perf_counter()
+                f()
+                walls[k].append((time.perf_counter() - t0) * 1e3)
+        return {k: {"median": round(sorted(v)[len(v) // 2], 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in walls.items()}
+
+    for name, flags in (("checked", 0), ("trusted", cp.PAIRING_TRUSTED)):
+        def per_proof():
+            assert not verifier.verify(pr, pu, flags=flags).any()
+
+        def all_():
+            v, path = verifier.verify_all(pr, w, pu, flags=flags)
+            assert not v.any() and path == 0
+        wall = timed({"per_proof": per_proof, "all": all_})
+        prover.profile_begin()
+        all_()
+        prof = prover.profile_end()
+        out[name] = {"wall_ms": wall, "all_over_per_proof": round(wall["all"]["median"] / wall["per_proof"]["median"], 4),
+                     "us_per_proof": {k: round(v["median"] / n * 1e3, 3) for k, v in wall.items()},
+                     "all_kernels_ms": {k: round(v["total_ms"], 4) for k, v in prof.items() if k.startswith(("pairing_", "groth16_", "msm_"))}}
+    return out
+
+
+def run_all_one_bad(prover, verifier, proofs, pubs, n, reps):
+    idx = np.arange(n) % len(proofs)
+    pr, pu = np.ascontiguousarray(proofs[idx]), np.ascontiguousarray(pubs[idx])
+    pr[n // 2, 36:48] = pr[n // 2 + 1, 36:48]
+    w = np.frombuffer(np.random.default_rng(n + 1).bytes(16 * n), np.uint64).reshape(n, 2) | np.uint64(1)
+    want = verifier.verify(pr, pu)
+    assert want.sum() == 1 and want[n // 2] == 1
+    walls = {"per_proof": [], "all": []}
+    for r in range(reps + 1):                                    # the first repeat is the warm-up
+        t0 = time.perf_counter()
+        got = verifier.verify(pr, pu)
+        t1 = time.perf_counter()
+        v, path = verifier.verify_all(pr, w, pu)
+        t2 = time.perf_counter()
+        assert (got == want).all() and (v == want).all() and path == 1
+        if r:
+            walls["per_proof"].append((t1 - t0) * 1e3)
+            walls["all"].append((t2 - t1) * 1e3)
+    wall = {k: {"median": round(sorted(v)[len(v) // 2], 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in walls.items()}
+    return {"n": n, "reps": reps, "bad_proofs": 1, "path": 1, "wall_ms": wall, "all_over_per_proof": round(wall["all"]["median"] / wall["per_proof"]["median"], 4)}
+
+
+def main_all(sizes, reps):
+    p = cp.Prover(0)
+    out = {"tool": "tools/bench_pairing.py --all", "method": "one process; per batch size both legs are warmed up once, then alternate within each of `reps` "
+           "repeats; wall = host clock around the synchronous call (staging and verdict copies included), median / min / max; kernels = device events "
+           "of one further profiled verify_all call; the weights are 128 random bits per proof", "n_public": N_PUBLIC, "kernel_registers": None, "sizes": []}
+    try:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import kernel_meta
+        new = ("k_scale_g1", "k_fr_weighted_sums", "k_gt_product")
+        out["kernel_registers"] = [{k: r[k] for k in ("name", "vgpr", "agpr", "vgpr_spill", "scratch", "lds")} for r in kernel_meta.kernels() if r["name"].endswith(new)]
+    except Exception as e:
+        out["kernel_registers"] = "unavailable: %s" % e
+    verifier, proofs, pubs = make_key_and_proofs(p)
+    for n in sizes:
+        out["sizes"].append(run_all(p, verifier, proofs, pubs, n, reps))
+        print("all", json.dumps(out["sizes"][-1]), flush=True)
+    out["one_bad"] = run_all_one_bad(p, verifier, proofs, pubs, max(sizes), reps) if max(sizes) >= 4 else None
+    verifier.close()
+    p.close()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "groth16_verify_all.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def measure(prover, call, reps, n, products):
     call()                                   # warm-up
     wall = []
@@ -212,6 +302,9 @@ if __name__ == "__main__":
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5
     if "--city" in sys.argv:
         main_city(sizes, reps)
+        sys.exit(0)
+    if "--all" in sys.argv:
+        main_all(sizes, reps)
         sys.exit(0)
     p = cp.Prover(0)
     counts = fp_product_counts()
