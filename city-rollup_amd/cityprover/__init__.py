@@ -527,6 +527,7 @@ def set_gates(circuit, gate_list, num_selectors):
     """gate_list: [(type, selector_index, group_start, group_end, param[, param2[, param3]])] in gate-index order."""
     arr = (Gate * len(gate_list))(*[Gate(*(tuple(g) + (0,) * (7 - len(g)))) for g in gate_list])
     circuit.prover._check(circuit.prover.lib.cp_circuit_set_gates(circuit.handle, arr, len(gate_list), num_selectors))
+    circuit.n_gates = len(gate_list)
 
 
 def prove_batch_dev(prover, circuits, public_inputs, wires_ptr, pow_overrides=None):
@@ -1361,6 +1362,7 @@ def load_circuit_file(prover, path):
     c = Circuit.__new__(Circuit)
     c.prover, c.handle, c.shape = prover, h, Shape()
     prover._check(prover.lib.cp_circuit_shape(h, ctypes.byref(c.shape), None))
+    c.n_gates = circuit_file_info(path)["n_gates"]
     return c
 
 
@@ -1955,3 +1957,106 @@ def stark_verify_batch(prover, desc, challengers, proofs, publics=None, globals_
     for i, c in enumerate(challengers):
         ctypes.memmove(ctypes.byref(c), ctypes.byref(ch[i]), ctypes.sizeof(ChallengerState))
     return [(int(v["status"]), int(v["query"]), int(v["detail"])) for v in out[:B]]
+
+
+# ---- does the witness satisfy the circuit, and where not? (include/cityprover.h; INTEGRATION.md "When a proof does not verify") ----
+class WitnessReport(ctypes.Structure):
+    """cp_witness_report"""
+    _fields_ = [("n_gate_violations", ctypes.c_uint64), ("n_copy_violations", ctypes.c_uint64), ("n_sigma_undecodable", ctypes.c_uint64),
+                ("n_noncanonical", ctypes.c_uint64), ("gate_row", ctypes.c_int64), ("gate_index", ctypes.c_int32), ("gate_type", ctypes.c_int32),
+                ("constraint", ctypes.c_int32), ("constraint_value", ctypes.c_uint64), ("copy_row", ctypes.c_int64), ("copy_column", ctypes.c_int32),
+                ("copy_to_row", ctypes.c_int64), ("copy_to_column", ctypes.c_int32), ("copy_value", ctypes.c_uint64), ("copy_to_value", ctypes.c_uint64),
+                ("sigma_row", ctypes.c_int64), ("sigma_column", ctypes.c_int32), ("noncanonical_row", ctypes.c_int64),
+                ("noncanonical_column", ctypes.c_int32)]
+
+
+class AirCheckReport(ctypes.Structure):
+    """cp_air_check_report"""
+    _fields_ = [("n_violations", ctypes.c_uint64), ("row", ctypes.c_int64), ("sink", ctypes.c_int64), ("sink_kind", ctypes.c_int32),
+                ("value", ctypes.c_uint64)]
+
+
+ABI["cp_circuit_check_witness_dev"] = (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp), ctypes.POINTER(_u64p), ctypes.POINTER(ctypes.c_size_t),
+                                                      _vp, ctypes.POINTER(WitnessReport), _u64p])
+ABI["cp_circuit_check_witness"] = (ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_size_t, ctypes.POINTER(WitnessReport), _u64p])
+ABI["cp_air_check_rows_dev"] = (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_size_t, _u64p, _u64p, _u64p, ctypes.POINTER(AirCheckReport), _u64p])
+ABI["cp_stark_check_trace"] = (ctypes.c_int, [_vp, ctypes.POINTER(StarkDesc), _vp, ctypes.c_int, _u64p, _u64p, _u64p, ctypes.POINTER(AirCheckReport), _u64p])
+
+
+def _report_dict(r, extra):
+    d = {f: int(getattr(r, f)) for f, _ in r._fields_}
+    d.update(extra)
+    return d
+
+
+def check_witness_batch_dev(prover, circuits, public_inputs, wires_ptr):
+    """cp_circuit_check_witness_dev: wires_ptr = device [proof][num_wires][n], arguments as prove_batch_dev. One dict per witness: the
+    fields of cp_witness_report, and "per_gate" = the count of violated (row, constraint) pairs of every gate index."""
+    B = len(circuits)
+    cs = (_vp * max(B, 1))(*[c.handle for c in circuits])
+    pis = [_as_u64(p) for p in public_inputs]
+    pi_ptrs = (_u64p * max(B, 1))(*[_ptr(p) if p.size else None for p in pis])
+    n_pis = (ctypes.c_size_t * max(B, 1))(*[p.size for p in pis])
+    reports = (WitnessReport * max(B, 1))()
+    per_gate = np.zeros((max(B, 1), 32), np.uint64)   # at most 32 gates per circuit; the library writes n_proofs x n_gates
+    prover._check(prover.lib.cp_circuit_check_witness_dev(prover.ctx, B, cs, pi_ptrs, n_pis, wires_ptr, reports, _ptr(per_gate)))
+    ng = getattr(circuits[0], "n_gates", None)   # None: the gate list was set behind this binding's back
+    flat = per_gate.reshape(-1)
+    out = []
+    for i in range(B):
+        pg = [int(v) for v in flat[i * ng:(i + 1) * ng]] if ng is not None else None
+        out.append(_report_dict(reports[i], {"per_gate": pg}))
+    return out
+
+
+def check_witness(circuit, wires, public_inputs):
+    """cp_circuit_check_witness: one witness [num_wires][n] in host memory -> the dict of check_witness_batch_dev"""
+    pr = circuit.prover
+    w, pi = _as_u64(wires), _as_u64(public_inputs)
+    if w.size != circuit.shape.num_wires << circuit.shape.degree_bits:
+        raise ValueError("wires must be [num_wires][n]")
+    r = WitnessReport()
+    per_gate = np.zeros(32, np.uint64)
+    pr._check(pr.lib.cp_circuit_check_witness(circuit.handle, _ptr(w), _ptr(pi) if pi.size else None, pi.size, ctypes.byref(r), _ptr(per_gate)))
+    ng = getattr(circuit, "n_gates", None)
+    return _report_dict(r, {"per_gate": [int(v) for v in per_gate[:ng]] if ng is not None else None})
+
+
+def _air_check_result(r, per_sink):
+    return _report_dict(r, {"per_sink": [int(v) for v in per_sink]})
+
+
+def _air_check_rows(self, cols, publics=None, globals_=None, challenges=None):
+    """cp_air_check_rows_dev on a host array: cols (n_columns, n) in natural row order -> the fields of cp_air_check_report and
+    "per_sink" = the number of violated rows of every sink"""
+    v = _as_u64(cols)
+    n = v.shape[1]
+    d = self.prover.to_device(v)
+    try:
+        return self.check_rows_dev(d.ptr, n, publics, globals_, challenges)
+    finally:
+        d.free()
+
+
+def _air_check_rows_dev(self, cols_ptr, n, publics=None, globals_=None, challenges=None):
+    (pp, gp, cp_), keep = zip(*[_opt_u64(x) for x in (publics, globals_, challenges)])
+    r = AirCheckReport()
+    per_sink = np.zeros(max(self.info()["n_constraints"], 1), np.uint64)
+    self.prover._check(self.prover.lib.cp_air_check_rows_dev(self.prover.ctx, self.handle, cols_ptr, n, pp, gp, cp_, ctypes.byref(r), _ptr(per_sink)))
+    return _air_check_result(r, per_sink[:self.info()["n_constraints"]])
+
+
+AirProgram.check_rows = _air_check_rows
+AirProgram.check_rows_dev = _air_check_rows_dev
+
+
+def stark_check_trace(prover, desc, trace, publics=None, globals_=None, round_challenges=None, n_constraints=None):
+    """cp_stark_check_trace: trace (n_trace_columns, n) host array; the extended columns are filled under round_challenges. n_constraints:
+    the number of sinks of desc.constraints, for "per_sink" (None: not returned)."""
+    t = _as_u64(trace)
+    (pp, gp, rp), keep = zip(*[_opt_u64(x) for x in (publics, globals_, round_challenges)])
+    r = AirCheckReport()
+    per_sink = np.zeros(max(n_constraints or 0, 1), np.uint64)
+    prover._check(prover.lib.cp_stark_check_trace(prover.ctx, ctypes.byref(desc), t.ctypes.data, 0, pp, gp, rp, ctypes.byref(r),
+                                                  _ptr(per_sink) if n_constraints is not None else None))
+    return _air_check_result(r, per_sink[:n_constraints or 0])

@@ -994,4 +994,6 @@ int cp_commit_dev(cp_ctx *ctx, const uint64_t *values, size_t k, int log_n, int 
 #include "air.h"
 #include "ext3.h"
 #include "stark.inc"
+#include "check.h"
+#include "check.inc"
 // (the BLS12-381 / Groth16 side is its own translation unit: bls.hip)

@@ -781,6 +781,75 @@ int cp_stark_verify_batch(cp_ctx *ctx, const cp_stark_desc *desc, size_t n_proof
                           cp_challenger_state *challengers, const uint8_t *const *proofs, const size_t *proof_lens,
                           size_t chunk_proofs, unsigned path_form, cp_verify_verdict *verdicts_out);
 
+/* ---- Does the witness satisfy the circuit, and where not? (INTEGRATION.md "When a proof does not verify") ----------------
+ * The proving calls above turn ANY wire matrix / trace into well-formed proof bytes; a violated witness shows only afterwards,
+ * as the verifier's "vanishing identity" / "quotient identity". These calls evaluate the constraints on the n ROWS themselves
+ * (not on the LDE coset), count what is broken and name the first. They prove nothing and change nothing the provers do.
+ *
+ * plonky2. Arguments as for cp_prove_batch / cp_prove: circuits of one shape and gate set (cp_circuit_set_gates),
+ * wires_values_dev [proof][num_wires][n]. The semantics are the quotient's own, restricted to the rows:
+ *   gates   gate gi BINDS a row when its filter is non-zero there: the product over the other gates r of its selector group of
+ *           (r - sv), sv the row's value of the gate's selector polynomial, times (0xFFFFFFFF - sv) when there are several
+ *           selector polynomials. A gate violation is a triple (row, gate index, constraint index k) with the gate binding the
+ *           row and its k-th constraint (plonky2's order, the order of csrc/gates.h) non-zero. constraint_value is that value,
+ *           canonical and unfiltered. PublicInputGate reads the hash of public_inputs_host, computed as the provers compute it.
+ *   copies  for a routed column c < num_routed_wires and a row i, the sigma value S = cs_values[num_constants + c][i] names the
+ *           cell (c', i') with S = k_is[c'] * omega_n^i'. A copy violation is a cell whose value differs from the cell it names.
+ *           A sigma value that names no cell is counted apart (n_sigma_undecodable) and never compared.
+ *   wires   values >= p are counted (n_noncanonical); every other check reads them mod p.
+ * The first of each kind is the lowest in the order row, then gate index, then constraint index (gates) or row, then column
+ * (the others); its fields are -1 (values: 0) when there is none. per_gate_out: NULL, or n_proofs x n_gates counts of
+ * (row, constraint) pairs per gate index; their sum is n_gate_violations.
+ * Returns CP_OK whatever the reports hold: a broken witness is a verdict on that item. CP_ERR_INVALID_ARG (the message names the
+ * proof) for a NULL argument, n_proofs == 0, a circuit without gates, circuits of different shapes or gate sets, a wrong number
+ * of public inputs, a public input >= p. CP_ERR_OOM for a refused allocation: the context stays usable and nothing is held. */
+typedef struct cp_witness_report {
+  uint64_t n_gate_violations;
+  uint64_t n_copy_violations;
+  uint64_t n_sigma_undecodable;
+  uint64_t n_noncanonical;
+  int64_t gate_row;
+  int32_t gate_index, gate_type, constraint;
+  uint64_t constraint_value;
+  int64_t copy_row;
+  int32_t copy_column;
+  int64_t copy_to_row;
+  int32_t copy_to_column;
+  uint64_t copy_value, copy_to_value;
+  int64_t sigma_row;
+  int32_t sigma_column;
+  int64_t noncanonical_row;
+  int32_t noncanonical_column;
+} cp_witness_report;
+int cp_circuit_check_witness_dev(cp_ctx *ctx, size_t n_proofs, cp_circuit *const *circuits,
+                                 const uint64_t *const *public_inputs_host, const size_t *n_public_inputs,
+                                 const uint64_t *wires_values_dev, cp_witness_report *reports_out, uint64_t *per_gate_out);
+/* one witness in host memory [num_wires][n], staged as cp_prove stages it */
+int cp_circuit_check_witness(cp_circuit *circuit, const uint64_t *wires_values_host, const uint64_t *public_inputs_host,
+                             size_t n_public_inputs, cp_witness_report *report_out, uint64_t *per_gate_out);
+/* STARK. cols_dev: n_columns x n, column-major, natural row order; n a power of two; the next row of row n - 1 is row 0. A sink
+ * (a constraint, numbered in program order as cp_air_program_eval_ext numbers them) BINDS a row by its kind: CP_AIR_ASSERT_ZERO
+ * every row, _TRANSITION rows 0 .. n - 2, _FIRST_ROW row 0 only, _LAST_ROW row n - 1 only. A violation is a pair (row, sink) with
+ * the sink binding the row and non-zero there; the first is the lowest in the order row, then sink (-1 / 0 when there is none),
+ * sink_kind its op code, value what it evaluates to. per_sink_out: NULL, or one count per sink. Refused: a map program, n not
+ * a power of two, NULL arguments, non-canonical publics / globals / challenges. */
+typedef struct cp_air_check_report {
+  uint64_t n_violations;
+  int64_t row, sink;
+  int32_t sink_kind;
+  uint64_t value;
+} cp_air_check_report;
+int cp_air_check_rows_dev(cp_ctx *ctx, const cp_air_program *constraints, const uint64_t *cols_dev, size_t n,
+                          const uint64_t *publics, const uint64_t *globals, const uint64_t *challenges,
+                          cp_air_check_report *report_out, uint64_t *per_sink_out);
+/* The trace of a STARK description: the extended columns are filled from desc->steps under the CALLER's round challenges
+ * (n_round_challenges of them; NULL when 0) exactly as cp_stark_prove fills them under the transcript's, then desc->constraints
+ * runs over the n_trace_columns + n_extended_columns columns. Refuses what cp_stark_prove refuses of a description and of a
+ * trace element >= p. */
+int cp_stark_check_trace(cp_ctx *ctx, const cp_stark_desc *desc, const uint64_t *trace_values, int trace_on_device,
+                         const uint64_t *publics, const uint64_t *globals, const uint64_t *round_challenges,
+                         cp_air_check_report *report_out, uint64_t *per_sink_out);
+
 /* ---- BLS12-381 G1 multi-scalar multiplication ---------------------------------
  * The G1 MSMs of the Groth16 wrap proof: replaces the CPU MSM inside `gnark_plonky2_wrapper::wrap_plonky2_proof`
  * (reference call sites: city_rollup_circuit/src/worker/toolbox/root.rs:296-304,
