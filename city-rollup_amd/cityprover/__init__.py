@@ -921,6 +921,26 @@ def fr_ntt_dev(prover, data_ptr, log_n, inverse=False, shift=None):
     prover._check(prover.lib.cp_ntt_bls12381_fr_dev(prover.ctx, data_ptr, log_n, flags, None if sh is None else _ptr(sh)))
 
 
+# ---- transforms of point vectors (the F_r NTT in the exponent) ----
+ABI["cp_point_ntt_bls12381_g1_dev"] = (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint])
+ABI["cp_point_ntt_bls12381_g2_dev"] = (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_uint])
+
+
+def point_ntt_g1_dev(prover, points, flags_buf, log_n, inverse=False, flags=None):
+    """cp_point_ntt_bls12381_g1_dev in place over a G1Points buffer of 2^log_n points and its flag buffer (as
+    G1Points.fixed_base returns them). flags: the raw flag word instead of `inverse` (refusal tests). Asynchronous."""
+    f = (NTT_INVERSE if inverse else 0) if flags is None else flags
+    prover._check(prover.lib.cp_point_ntt_bls12381_g1_dev(prover.ctx, points.buf.ptr if points is not None else None,
+                                                          flags_buf.ptr if flags_buf is not None else None, log_n, f))
+
+
+def point_ntt_g2_dev(prover, points, flags_buf, log_n, inverse=False, flags=None):
+    """point_ntt_g1_dev over a G2Points buffer (cp_point_ntt_bls12381_g2_dev)"""
+    f = (NTT_INVERSE if inverse else 0) if flags is None else flags
+    prover._check(prover.lib.cp_point_ntt_bls12381_g2_dev(prover.ctx, points.buf.ptr if points is not None else None,
+                                                          flags_buf.ptr if flags_buf is not None else None, log_n, f))
+
+
 def groth16_quotient(prover, a, b, c):
     """a, b, c: (n, 4) uint64 canonical F_r evaluations of (A w), (B w), (C w) on <omega_n> -> the n coefficients of
     h = (a b - c) / (x^n - 1) (cp_groth16_quotient_bls12381)."""
@@ -1076,6 +1096,51 @@ ABI["cp_groth16_key_pk"] = (ctypes.c_int, [_vp, ctypes.POINTER(Groth16Pk)])
 ABI["cp_groth16_key_vk"] = (ctypes.c_int, [_vp, ctypes.POINTER(Groth16Vk), _u64p, _u8p])
 
 
+# ---- a key without a trapdoor: setup from a powers-of-tau SRS, delta contributions (include/cityprover.h) ----
+GROTH16_SRS_CHECK_TORSION = 1
+
+
+class Groth16SrsDesc(ctypes.Structure):
+    _fields_ = [("log_size", ctypes.c_int), ("tau_g1", _u64p), ("tau_g2", _u64p), ("alpha_tau_g1", _u64p), ("beta_tau_g1", _u64p),
+                ("beta_g2", ctypes.c_uint64 * 24)]
+
+
+ABI["cp_groth16_srs_create_bls12381"] = (_vp, [_vp, ctypes.POINTER(Groth16SrsDesc), ctypes.c_uint])
+ABI["cp_groth16_srs_destroy"] = (None, [_vp])
+ABI["cp_groth16_setup_srs_bls12381"] = (_vp, [_vp, ctypes.POINTER(R1csDesc), ctypes.c_size_t, _vp])
+ABI["cp_groth16_key_contribute_bls12381"] = (ctypes.c_int, [_vp, _vp, _u64p, ctypes.POINTER(_vp)])
+ABI["cp_groth16_key_check_contribution_bls12381"] = (ctypes.c_int, [_vp, _vp, _vp, _u64p, ctypes.POINTER(ctypes.c_int)])
+
+
+class Groth16Srs:
+    """A phase-1 powers-of-tau SRS resident on the device (cp_groth16_srs_create_bls12381). Its points are checked one by one;
+    that the arrays belong together is the ceremony's to verify, not this library's."""
+
+    def __init__(self, prover, log_size, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, check_torsion=False, flags=None):
+        """tau_g1: (2^(L+1) - 1, 12) u64, tau_g2: (2^L, 24), alpha_tau_g1 / beta_tau_g1: (2^L, 12), beta_g2: 24 u64 - affine
+        canonical. flags: the raw flag word instead of check_torsion (refusal tests)."""
+        arrays = [_as_u64(a) for a in (tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1)]
+        n = 1 << log_size
+        for a, want in zip(arrays, ((2 * n - 1) * 12, n * 24, n * 12, n * 12)):
+            if a.size != want:
+                raise ValueError("an SRS array has %d words, log_size %d needs %d" % (a.size, log_size, want))
+        desc = Groth16SrsDesc()
+        desc.log_size = log_size
+        desc.tau_g1, desc.tau_g2, desc.alpha_tau_g1, desc.beta_tau_g1 = (_ptr(a) for a in arrays)
+        desc.beta_g2[:] = [int(v) for v in _as_u64(beta_g2).reshape(24)]
+        f = (GROTH16_SRS_CHECK_TORSION if check_torsion else 0) if flags is None else flags
+        self.prover, self.log_size = prover, log_size
+        self.handle = prover.lib.cp_groth16_srs_create_bls12381(prover.ctx, ctypes.byref(desc), f)
+        del arrays
+        if not self.handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+
+    def free(self):
+        if self.handle:
+            self.prover.lib.cp_groth16_srs_destroy(self.handle)
+            self.handle = None
+
+
 class Groth16Key:
     """A proving key resident on the device, with its verifying key (cp_groth16_setup_bls12381)."""
 
@@ -1094,6 +1159,36 @@ class Groth16Key:
         if not handle:
             raise CityProverError(prover.lib.cp_last_error(None).decode())
         return cls(prover, handle)
+
+    @classmethod
+    def setup_srs(cls, prover, n_constraints, n_wires, coeffs, matrices, n_public, srs, flags=0):
+        """cp_groth16_setup_srs_bls12381: the key of (tau, alpha, beta, gamma = 1, delta = 1) from a Groth16Srs, without any secret"""
+        desc, keep = r1cs_desc(n_constraints, n_wires, coeffs, matrices, flags)
+        handle = prover.lib.cp_groth16_setup_srs_bls12381(prover.ctx, ctypes.byref(desc), int(n_public), srs.handle)
+        del keep
+        if not handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+        return cls(prover, handle)
+
+    def contribute(self, d, prover=None):
+        """cp_groth16_key_contribute_bls12381: a new key with delta multiplied by the int d (the caller's secret), K and Z by 1 / d"""
+        p = prover or self.prover
+        dd = np.array([(int(d) >> (64 * j)) & (2**64 - 1) for j in range(4)], dtype=np.uint64)
+        out = ctypes.c_void_p()
+        p._check(p.lib.cp_groth16_key_contribute_bls12381(p.ctx, self.handle, _ptr(dd), ctypes.byref(out)))
+        return Groth16Key(p, out.value)
+
+    @staticmethod
+    def check_contribution(prover, before, after, weights):
+        """cp_groth16_key_check_contribution_bls12381: (verdict, reason). weights: n_private + 2^log_domain - 1 non-zero ints below
+        2^128 (or an (n, 2) u64 array), unpredictable to whoever made `after`."""
+        w = None
+        if weights is not None:
+            w = _as_u64(weights).reshape(-1, 2) if isinstance(weights, np.ndarray) else _weights128(weights, len(weights))
+        verdict = ctypes.c_int(-1)
+        prover._check(prover.lib.cp_groth16_key_check_contribution_bls12381(prover.ctx, before.handle, after.handle,
+                                                                            None if w is None else _ptr(w), ctypes.byref(verdict)))
+        return verdict.value, prover.lib.cp_last_error(prover.ctx).decode()
 
     def pk(self):
         """Groth16Pk: a view, valid until free()"""

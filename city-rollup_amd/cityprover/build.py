@@ -15,7 +15,8 @@ UNITS = {
     "cityprover.hip": ["poseidon.h", "poseidon_coop.h", "poseidon_tables.h", "merkle.h", "ntt.h", "ntt16.h", "fri.h", "transcript.h", "zs.h", "quotient.h", "gates.h",
                        "quotient.inc", "prover_tail.inc", "fri_engine.inc", "fri_prove.inc", "batcher.inc", "verify.inc", "fri_verify.h", "circuit_file.inc", "air.h", "ext3.h", "stark.inc", "check.h", "check.inc"],
     "bls.hip": ["bls12_381.h", "bls12_381_tables.h", "msm.h", "msm.inc", "bls12_381_fr.h", "fr_ntt.h", "fr_ntt.inc", "groth16.inc",
-                "groth16_pack.inc", "pairing.h", "bls_sqrt.h", "r1cs.h", "r1cs.inc", "fixed_base.h", "fixed_base.inc", "groth16_setup.h", "groth16_setup.inc", "groth16_key.h"],
+                "groth16_pack.inc", "pairing.h", "bls_sqrt.h", "r1cs.h", "r1cs.inc", "fixed_base.h", "fixed_base.inc", "groth16_setup.h", "groth16_setup.inc", "groth16_key.h",
+                "point_ntt.h", "point_ntt.inc", "groth16_srs.h", "groth16_srs.inc"],
     "pairing.hip": ["bls12_381.h", "bls12_381_tables.h", "bls12_381_fr.h", "pairing.h", "bls_sqrt.h"],
     "keyfile.hip": ["bls12_381.h", "bls12_381_tables.h", "pairing.h", "bls_sqrt.h", "groth16_key.h"],
 }

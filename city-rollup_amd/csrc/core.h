@@ -110,6 +110,7 @@ struct cp_ctx {
     uint64_t shift[4] = {0, 0, 0, 0};
   } fr_pow[2] = {{buf()}, {buf()}};  // [0]: forward (powers of the shift), [1]: inverse (powers of its inverse)
   DevBuf msm_ws = buf();  // grow-only workspace of the MSMs (counts, sorted indices, buckets)
+  DevBuf point_work = buf();  // grow-only Jacobian work array of the point transforms (point_ntt.inc)
   struct FixedBase {        // cached window table of the fixed-base multiplication (fixed_base.inc): a setup asks for one base per group
     DevBuf tab;
     bool valid = false;

@@ -1187,6 +1187,73 @@ cp_groth16_key *cp_groth16_key_load_file(cp_ctx *ctx, const char *path, unsigned
 int cp_groth16_key_file_info(const char *path, int verify_checksum, struct cp_groth16_key_file_info *info_out,
                              cp_groth16_vk *vk_out, uint64_t *ic_xy_out, uint8_t *ic_inf_out);
 
+/* ---- Transforms of point vectors: the NTT of cp_ntt_bls12381_fr_dev "in the exponent" ----
+ * In place over 2^log_n points in the library's internal affine form with their infinity flags (what the fixed-base
+ * multiplication writes): out_j = sum_k omega_n^(j k) P_k, omega_n = 7^((r-1)/n), natural order in and out; CP_NTT_INVERSE
+ * is the exact inverse, 1/n included. An output at infinity gets its flag and the group's standard generator as its entry;
+ * an input under a flag is the point at infinity whatever its entry holds. log_n from 0 to 28. Any other flag bit,
+ * CP_NTT_COSET included, is refused: there is no coset form. Radix 2, one lane per butterfly and stage, points Jacobian
+ * between the stages in a work array of the context, one inversion per four outputs at the end. Asynchronous on the
+ * context stream, like the other _dev entry points. */
+int cp_point_ntt_bls12381_g1_dev(cp_ctx *ctx, void *points_mont_dev, uint8_t *points_inf_dev, int log_n, unsigned flags);
+int cp_point_ntt_bls12381_g2_dev(cp_ctx *ctx, void *points_mont_dev, uint8_t *points_inf_dev, int log_n, unsigned flags);
+
+/* ---- A Groth16 key without a trapdoor: setup from a powers-of-tau SRS, and delta contributions ----
+ * Whoever knows the five scalars of cp_groth16_trapdoor can forge proofs: a key made by cp_groth16_setup_bls12381 is for
+ * tests and benchmarks. The deployable route has two steps.
+ *  1. A universal SRS - the output of a phase-1 ceremony: [tau^k]_1, [tau^k]_2, [alpha tau^k]_1, [beta tau^k]_1, [beta]_2 - is
+ *     specialised to a circuit. No secret is used: the Lagrange-basis points [L_j(tau)] are the inverse point transform of the
+ *     powers, the query points are sums over the columns of the R1CS matrices, Z_j = [tau^(j+N)]_1 - [tau^j]_1. The key is the
+ *     one cp_groth16_setup_bls12381 returns for (tau, alpha, beta, gamma = 1, delta = 1), byte for byte.
+ *  2. Parties re-randomise delta one after another: delta_1, delta_2 <- d delta_1, d delta_2, K_i <- K_i / d, Z_j <- Z_j / d.
+ *     The key is safe if one of them destroyed its d. Anyone checks a step from the two keys alone.
+ *
+ * srs_create: host arrays, affine canonical (12 u64 per G1 point, 24 per G2 point), copied and converted to the internal
+ * form. Every coordinate is checked to be canonical and every point to be on the curve / twist; with
+ * CP_GROTH16_SRS_CHECK_TORSION also [r]P = infinity. The first refused point is named by array and index. tau_g1[0] and
+ * tau_g2[0] must be the standard generators. NOT checked: that the arrays are consistent with one another - that they are
+ * the powers of one tau, and alpha / beta times them. That takes pairings against the ceremony's transcript and is the
+ * ceremony's to verify; an SRS is taken as given, like a key file. A key from an inconsistent SRS proves nothing. The handle
+ * lives on the context's device, serves any context of that device and may be destroyed after it; NULL is a no-op.
+ *
+ * setup_srs: every refusal cp_groth16_setup_bls12381 makes of the system and of n_public, in its words (the private wire
+ * whose K point would be infinity included); and a system whose log_domain exceeds the SRS's log_size. A smaller domain
+ * uses the prefix of each array. The result is an ordinary key: cp_groth16_key_pk / _vk, the provers, the verifier and the
+ * key files take it unchanged. Expect seconds where the trapdoor setup takes a fraction of one: every
+ * butterfly of the transforms is a 255-bit scalar multiplication. It runs once per circuit.
+ *
+ * key_contribute: d canonical and not zero, the caller's (the library draws no randomness) and the caller's to destroy.
+ * *key_out is a new key on the same device; the input key is not modified. Everything but delta_g1, delta_g2 (proving and
+ * verifying key), k_g1 and z_g1 is copied.
+ *
+ * key_check_contribution: weights_host: (n_private + 2^log_domain - 1) x 2 u64, a non-zero 128-bit value per K and Z point,
+ * with the convention and the warning of cp_groth16_verify_all_bls12381: they MUST be unpredictable to whoever made `after`.
+ * *verdict_out: 0 `after` is `before` under some non-zero multiplier of delta; 1 a part that must not change differs
+ * (cp_last_error names it); 2 e(delta_1', delta_2) != e(delta_1, delta_2'); 3 e(S', delta_2') != e(S, delta_2) for
+ * S = sum rho_i K_i + sum sigma_j Z_j over each key; 4 a delta point of `after` is off the curve or outside the r-torsion. The
+ * call returns CP_OK whatever the verdict; CP_ERR_INVALID_ARG for a NULL argument and for a weight of zero (the message names
+ * its index). Two MSMs per key and two products of two pairings. Proofs of knowledge of d and the hashing of a transcript are
+ * the ceremony's protocol layer and stay with the caller.
+ * A refused allocation is CP_ERR_OOM in all of these; the context stays usable and nothing is held. */
+typedef struct cp_groth16_srs_desc {
+  int log_size;                 /* L >= 1: serves every domain of up to 2^L points */
+  const uint64_t *tau_g1;       /* (2^(L+1) - 1) x 12: [tau^k]_1 */
+  const uint64_t *tau_g2;       /* 2^L x 24:           [tau^k]_2 */
+  const uint64_t *alpha_tau_g1; /* 2^L x 12 */
+  const uint64_t *beta_tau_g1;  /* 2^L x 12 */
+  uint64_t beta_g2[24];
+} cp_groth16_srs_desc;
+#define CP_GROTH16_SRS_CHECK_TORSION 1u
+typedef struct cp_groth16_srs cp_groth16_srs;
+cp_groth16_srs *cp_groth16_srs_create_bls12381(cp_ctx *ctx, const cp_groth16_srs_desc *desc, unsigned flags);
+void cp_groth16_srs_destroy(cp_groth16_srs *srs);
+cp_groth16_key *cp_groth16_setup_srs_bls12381(cp_ctx *ctx, const cp_r1cs_desc *system, size_t n_public,
+                                              const cp_groth16_srs *srs);
+int cp_groth16_key_contribute_bls12381(cp_ctx *ctx, const cp_groth16_key *key, const uint64_t d[4],
+                                       cp_groth16_key **key_out);
+int cp_groth16_key_check_contribution_bls12381(cp_ctx *ctx, const cp_groth16_key *before, const cp_groth16_key *after,
+                                               const uint64_t *weights_host, int *verdict_out);
+
 #ifdef __cplusplus
 }
 #endif
