@@ -1110,11 +1110,15 @@ ABI["cp_groth16_srs_destroy"] = (None, [_vp])
 ABI["cp_groth16_setup_srs_bls12381"] = (_vp, [_vp, ctypes.POINTER(R1csDesc), ctypes.c_size_t, _vp])
 ABI["cp_groth16_key_contribute_bls12381"] = (ctypes.c_int, [_vp, _vp, _u64p, ctypes.POINTER(_vp)])
 ABI["cp_groth16_key_check_contribution_bls12381"] = (ctypes.c_int, [_vp, _vp, _vp, _u64p, ctypes.POINTER(ctypes.c_int)])
+ABI["cp_groth16_srs_unit_bls12381"] = (_vp, [_vp, ctypes.c_int])
+ABI["cp_groth16_srs_contribute_bls12381"] = (ctypes.c_int, [_vp, _vp, _u64p, _u64p, _u64p, ctypes.POINTER(_vp)])
+ABI["cp_groth16_srs_points_bls12381"] = (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_int), _u64p, _u64p, _u64p, _u64p, _u64p])
+ABI["cp_groth16_srs_check_bls12381"] = (ctypes.c_int, [_vp, _vp, _u64p, ctypes.POINTER(ctypes.c_int)])
 
 
 class Groth16Srs:
-    """A phase-1 powers-of-tau SRS resident on the device (cp_groth16_srs_create_bls12381). Its points are checked one by one;
-    that the arrays belong together is the ceremony's to verify, not this library's."""
+    """A phase-1 powers-of-tau SRS resident on the device (cp_groth16_srs_create_bls12381). Its points are checked one by one
+    when it is created; check() tells whether the arrays belong together. unit() and contribute() make and extend one."""
 
     def __init__(self, prover, log_size, tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1, beta_g2, check_torsion=False, flags=None):
         """tau_g1: (2^(L+1) - 1, 12) u64, tau_g2: (2^L, 24), alpha_tau_g1 / beta_tau_g1: (2^L, 12), beta_g2: 24 u64 - affine
@@ -1134,6 +1138,56 @@ class Groth16Srs:
         del arrays
         if not self.handle:
             raise CityProverError(prover.lib.cp_last_error(None).decode())
+
+    @classmethod
+    def _of_handle(cls, prover, log_size, handle):
+        self = cls.__new__(cls)
+        self.prover, self.log_size, self.handle = prover, log_size, handle
+        return self
+
+    @classmethod
+    def unit(cls, prover, log_size):
+        """cp_groth16_srs_unit_bls12381: the SRS of tau = alpha = beta = 1, the start of a ceremony (worthless as an SRS)"""
+        handle = prover.lib.cp_groth16_srs_unit_bls12381(prover.ctx, int(log_size))
+        if not handle:
+            raise CityProverError(prover.lib.cp_last_error(None).decode())
+        return cls._of_handle(prover, int(log_size), handle)
+
+    def contribute(self, t, a, b, prover=None):
+        """cp_groth16_srs_contribute_bls12381: a new Groth16Srs with tau, alpha, beta multiplied by the ints t, a, b (the caller's
+        secrets); applied to unit() it is the SRS of (t, a, b)"""
+        p = prover or self.prover
+        s = [np.array([(int(v) >> (64 * j)) & (2**64 - 1) for j in range(4)], dtype=np.uint64) for v in (t, a, b)]
+        out = ctypes.c_void_p()
+        p._check(p.lib.cp_groth16_srs_contribute_bls12381(p.ctx, self.handle, _ptr(s[0]), _ptr(s[1]), _ptr(s[2]), ctypes.byref(out)))
+        return Groth16Srs._of_handle(p, self.log_size, out.value)
+
+    def points(self, prover=None):
+        """cp_groth16_srs_points_bls12381: the five parts of cp_groth16_srs_desc as a dict of u64 arrays, affine canonical - what
+        __init__ takes"""
+        p = prover or self.prover
+        L = ctypes.c_int(-1)
+        p._check(p.lib.cp_groth16_srs_points_bls12381(p.ctx, self.handle, ctypes.byref(L), None, None, None, None, None))
+        n = 1 << L.value
+        out = {"log_size": L.value, "tau_g1": np.zeros((2 * n - 1, 12), np.uint64), "tau_g2": np.zeros((n, 24), np.uint64),
+               "alpha_tau_g1": np.zeros((n, 12), np.uint64), "beta_tau_g1": np.zeros((n, 12), np.uint64), "beta_g2": np.zeros(24, np.uint64)}
+        p._check(p.lib.cp_groth16_srs_points_bls12381(p.ctx, self.handle, None, _ptr(out["tau_g1"]), _ptr(out["tau_g2"]), _ptr(out["alpha_tau_g1"]),
+                                                      _ptr(out["beta_tau_g1"]), _ptr(out["beta_g2"])))
+        return out
+
+    def check(self, weights, prover=None):
+        """cp_groth16_srs_check_bls12381: (verdict, reason). weights: 5 * 2^log_size - 5 non-zero ints below 2^128 (or an (n, 2) u64
+        array), one per adjacent pair of tau_g1, tau_g2, alpha_tau_g1, beta_tau_g1 in this order, unpredictable to whoever made
+        the SRS."""
+        p = prover or self.prover
+        w = None
+        if weights is not None:
+            w = _as_u64(weights).reshape(-1, 2) if isinstance(weights, np.ndarray) else _weights128(weights, len(weights))
+            if w.shape[0] != 5 * (1 << self.log_size) - 5:
+                raise ValueError("an SRS of log_size %d takes %d weights, not %d" % (self.log_size, 5 * (1 << self.log_size) - 5, w.shape[0]))
+        verdict = ctypes.c_int(-1)
+        p._check(p.lib.cp_groth16_srs_check_bls12381(p.ctx, self.handle, None if w is None else _ptr(w), ctypes.byref(verdict)))
+        return verdict.value, p.lib.cp_last_error(p.ctx).decode()
 
     def free(self):
         if self.handle:

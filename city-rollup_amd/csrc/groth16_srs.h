@@ -9,6 +9,8 @@
 //   k_z                                Z_j = [tau^(j+N)]_1 - [tau^j]_1
 //   k_check_points                     the curve equation and, if asked, [r]P = infinity, for the points of an SRS
 //   k_first_flag / k_differs           the lowest set flag of an array; whether two arrays differ
+//   k_scale_each                       phase 1: every point of an SRS array times its own scalar c t^k
+//   k_fill / k_canonical               the unit SRS; an SRS array as affine canonical words for the host
 //
 // A term's class (r1cs.h) chooses its action: +1 / -1 one mixed addition, a one-limb constant a short multiple, anything else
 // the full multiple. All results are Jacobian points in a work array; pointntt::k_finish makes them affine with flags.
@@ -165,6 +167,53 @@ __global__ __launch_bounds__(LANES<F>, WAVES<F>) void k_check_points(const Affin
   for (int w = 0; w < SCALAR_WORDS; w++) ks[threadIdx.x][w] = order.w[w];
   affine_mul_u256_at<F>(&prod[threadIdx.x], pts + i, ks[threadIdx.x]);
   if (!bls::jac_is_inf(prod[threadIdx.x])) atomicMin(&first_bad[1], (unsigned long long)i);
+}
+
+// ---- phase 1: the SRS itself (cp_groth16_srs_unit / _contribute / _points) ----
+// The scalar of entry k of an array under a contribution (t, a, b): powers[k] = t^k, times the array's constant where it has
+// one (a for alpha_tau_g1, b for beta_tau_g1; the two tau arrays have none). One table of t^k, k < 2n - 1, serves all four.
+struct EachScalar {
+  const blsfr::Fr *powers;  // Montgomery
+  blsfr::Fr c;              // Montgomery; read only with has_c
+  int has_c;
+};
+GL_HD void each_scalar(const EachScalar &S, size_t k, uint32_t *out) {
+  blsfr::Fr s = S.powers[k];
+  if (S.has_c) s = blsfr::fr_mul(s, S.c);
+  blsfr::fr_to_canonical(s, out);
+}
+// what a lane of k_scale_each does: *prod = (c t^k) * pts[k], the scalar through the lane's eight words at ks
+template <class F> GL_HD void scale_each_lane(JacT<F> *prod, uint32_t *ks, const AffineT<F> *pts, size_t k, const EachScalar &S) {
+  each_scalar(S, k, ks);
+  affine_mul_u256_at<F>(prod, pts + k, ks);
+}
+// work[k] = scalar(k) * pts[k]: a lane per point, each under its OWN scalar, so the conditional addition diverges inside a
+// wave (255 doublings and up to 255 mixed additions per wave, where pointntt::k_scale pays the additions of one scalar). The
+// source is the affine array itself: the mixed addition, and no load pass.
+template <class F>
+__global__ __launch_bounds__(LANES<F>, WAVES<F>) void k_scale_each(const AffineT<F> *__restrict__ pts, size_t n, EachScalar S, JacT<F> *__restrict__ work) {
+  __shared__ JacT<F> prod[LANES<F>];
+  __shared__ uint32_t ks[LANES<F>][SCALAR_WORDS];
+  const size_t k = (size_t)blockIdx.x * LANES<F> + threadIdx.x;
+  if (k >= n) return;  // no barrier below: a lane reads only what it wrote
+  scale_each_lane<F>(&prod[threadIdx.x], ks[threadIdx.x], pts, k, S);
+  work[k] = prod[threadIdx.x];
+}
+// out[i] = p for every i < n: the unit SRS
+template <class F>
+__global__ __launch_bounds__(256) void k_fill(AffineT<F> p, size_t n, AffineT<F> *__restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = p;
+}
+// the internal form -> affine canonical words (x then y, Field<F>::WORDS each): what cp_groth16_srs_desc holds
+template <class F>
+__global__ __launch_bounds__(256) void k_canonical(const AffineT<F> *__restrict__ pts, size_t n, uint32_t *__restrict__ out) {
+  constexpr int W = Field<F>::WORDS;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const AffineT<F> a = pts[i];
+  Field<F>::to_canonical(a.x, out + 2 * W * i);
+  Field<F>::to_canonical(a.y, out + 2 * W * i + W);
 }
 
 __global__ void k_first_flag(const uint8_t *__restrict__ inf, size_t n, unsigned long long *first) {

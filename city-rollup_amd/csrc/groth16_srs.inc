@@ -5,6 +5,9 @@
 //                                         Z_j = [tau^(j+N)] - [tau^j]; the key has gamma = delta = 1
 //   cp_groth16_key_contribute_bls12381    delta <- d delta, K and Z <- K / d and Z / d, into a new key
 //   cp_groth16_key_check_contribution_*   that step checked from the two keys: two MSMs per key, two products of two pairings
+//   cp_groth16_srs_unit / _contribute     phase 1 itself: the SRS of tau = alpha = beta = 1, and every point times its own c t^k
+//   cp_groth16_srs_points / _check        the SRS back on the host; that its arrays belong together: eight MSMs over adjacent
+//                                         pairs under the caller's weights, five products of two pairings in one call
 // Included by bls.hip after groth16_setup.inc and point_ntt.inc.
 struct cp_groth16_srs {
   explicit cp_groth16_srs(int dev) : device(dev), mem(dev_pool(), dev) {}
@@ -509,6 +512,223 @@ int groth16_check_contribution_run(cp_ctx *ctx, const cp_groth16_key *before, co
   return contribution_verdict(ctx, 0, verdict, "the key after is the key before under a non-zero multiplier of delta");
 }
 
+// ---- phase 1: the unit SRS, a contribution, the read-back, the consistency check ----
+int srs_on_ctx_device(cp_ctx *ctx, const cp_groth16_srs *srs) {
+  if (srs->device != ctx->device) return set_error(ctx, CP_ERR_INVALID_ARG, "the SRS lives on device %d, the context on device %d", srs->device, ctx->device);
+  return CP_OK;
+}
+
+template <class F>
+int srs_fill(cp_ctx *ctx, cp_groth16_srs *srs, size_t n, void **out) {
+  bls::AffineT<F> gen;
+  CP_TRY(generator_mont<F>(ctx, &gen));
+  const size_t bytes = n * sizeof(bls::AffineT<F>);
+  CP_TRY(alloc_status(ctx, srs->mem.alloc(out, bytes), bytes));
+  LAUNCH(ctx, IS_G1<F> ? "srs_fill_g1" : "srs_fill_g2", g16srs::k_fill<F>, dim3(blocks_for(n, 256)), dim3(256), gen, n, (bls::AffineT<F> *)*out);
+  return CP_OK;
+}
+
+int groth16_srs_unit_run(cp_ctx *ctx, int log_size, cp_groth16_srs *srs) {
+  if (log_size < 1 || log_size > 28) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS: log_size %d out of range (1 .. 28)", log_size);
+  const size_t n = (size_t)1 << log_size;
+  srs->log_size = log_size;
+  CP_TRY(srs_fill<bls::Fp>(ctx, srs, 2 * n - 1, &srs->tau_g1));
+  CP_TRY(srs_fill<bls::Fp2>(ctx, srs, n, &srs->tau_g2));
+  CP_TRY(srs_fill<bls::Fp>(ctx, srs, n, &srs->alpha_tau_g1));
+  CP_TRY(srs_fill<bls::Fp>(ctx, srs, n, &srs->beta_tau_g1));
+  memcpy(srs->alpha_g1, BLS_G1_GEN, sizeof srs->alpha_g1);
+  memcpy(srs->beta_g1, BLS_G1_GEN, sizeof srs->beta_g1);
+  memcpy(srs->beta_g2, BLS_G2_GEN, sizeof srs->beta_g2);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CP_OK;
+}
+
+int srs_scalar(cp_ctx *ctx, const uint64_t v[4], const char *name, blsfr::Fr *out) {
+  if (!(v[0] | v[1] | v[2] | v[3])) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS contribution: %s is zero", name);
+  if (!blsfr::fr_is_canonical((const uint32_t *)v)) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS contribution: %s is not canonical (>= r)", name);
+  *out = blsfr::fr_from_canonical((const uint32_t *)v);
+  return CP_OK;
+}
+
+// *dst (a new array of `out`) [k] = scalar(k) * in[k] for k < n; a result at infinity is refused by array and lowest index
+template <class F>
+int scale_each_set(cp_ctx *ctx, cp_groth16_srs *out, const void *in, size_t n, const g16srs::EachScalar &S, const char *name, bls::JacT<F> *work, uint8_t *flags,
+                   unsigned long long *slot, void **dst) {
+  const size_t bytes = n * sizeof(bls::AffineT<F>);
+  CP_TRY(alloc_status(ctx, out->mem.alloc(dst, bytes), bytes));
+  LAUNCH(ctx, IS_G1<F> ? "srs_scale_each_g1" : "srs_scale_each_g2", g16srs::k_scale_each<F>, dim3(blocks_for(n, fixedbase::LANES<F>)), dim3(fixedbase::LANES<F>),
+         (const bls::AffineT<F> *)in, n, S, work);
+  CP_TRY(point_finish<F>(ctx, work, n, nullptr, *dst, flags));
+  unsigned long long first = 0;
+  CP_TRY(first_flag(ctx, flags, n, slot, &first));
+  if (first != ~0ull)
+    return set_error(ctx, CP_ERR_INVALID_ARG, "SRS contribution: %s[%llu] times its scalar is the point at infinity (a point outside the r-torsion)", name, first);
+  return CP_OK;
+}
+
+// one entry of a G1 array of the SRS as affine canonical words
+int srs_g1_entry(cp_ctx *ctx, const void *arr, size_t index, uint64_t out[12]) {
+  bls::Affine p;
+  HIP_TRY(ctx, hipMemcpyAsync(&p, (const bls::Affine *)arr + index, sizeof p, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  uint32_t cw[24];
+  bls::fp_to_canonical(p.x, cw);
+  bls::fp_to_canonical(p.y, cw + 12);
+  memcpy(out, cw, sizeof cw);
+  return CP_OK;
+}
+
+int groth16_srs_contribute_run(cp_ctx *ctx, const cp_groth16_srs *srs, const uint64_t t[4], const uint64_t a[4], const uint64_t b[4], cp_groth16_srs *out) {
+  blsfr::Fr tf, af, bf;
+  CP_TRY(srs_scalar(ctx, t, "t", &tf));
+  CP_TRY(srs_scalar(ctx, a, "a", &af));
+  CP_TRY(srs_scalar(ctx, b, "b", &bf));
+  CP_TRY(srs_on_ctx_device(ctx, srs));
+  const size_t n = (size_t)1 << srs->log_size, n1 = 2 * n - 1;
+  out->log_size = srs->log_size;
+  // [b] beta_g2 on the host, under the kernels
+  bls::Jac2 b2;
+  CP_TRY(point_in<bls::Fp2>(ctx, srs->beta_g2, "the SRS's beta_g2", &b2));
+  int inf2 = 0;
+  jac_out<bls::Fp2>(jac_mul_scalar(b2, b), out->beta_g2, &inf2);
+  if (inf2) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS contribution: beta_g2 times b is the point at infinity (a point outside the r-torsion)");
+  DevBag tmp = ctx->bag();
+  blsfr::Fr *powers = nullptr;
+  uint8_t *flags = nullptr;
+  unsigned long long *slot = nullptr;
+  CP_TRY(alloc_status(ctx, tmp.alloc(&powers, n1 * sizeof(blsfr::Fr)), n1 * sizeof(blsfr::Fr)));
+  CP_TRY(alloc_status(ctx, tmp.alloc(&flags, n1), n1));
+  CP_TRY(alloc_status(ctx, tmp.alloc(&slot, 8), 8));
+  void *w = nullptr;  // one work array for the four sets, sized for the largest: n points of G2
+  CP_TRY(point_work(ctx, n * sizeof(bls::Jac2) > n1 * sizeof(bls::Jac) ? n * sizeof(bls::Jac2) : n1 * sizeof(bls::Jac), &w));
+  LAUNCH(ctx, "fr_powers", frntt::k_powers, dim3(blocks_for(n1, 256)), dim3(256), tf, n1, powers);
+  const g16srs::EachScalar plain{powers, tf, 0}, with_a{powers, af, 1}, with_b{powers, bf, 1};
+  CP_TRY(scale_each_set<bls::Fp>(ctx, out, srs->tau_g1, n1, plain, "tau_g1", (bls::Jac *)w, flags, slot, &out->tau_g1));
+  CP_TRY(scale_each_set<bls::Fp2>(ctx, out, srs->tau_g2, n, plain, "tau_g2", (bls::Jac2 *)w, flags, slot, &out->tau_g2));
+  CP_TRY(scale_each_set<bls::Fp>(ctx, out, srs->alpha_tau_g1, n, with_a, "alpha_tau_g1", (bls::Jac *)w, flags, slot, &out->alpha_tau_g1));
+  CP_TRY(scale_each_set<bls::Fp>(ctx, out, srs->beta_tau_g1, n, with_b, "beta_tau_g1", (bls::Jac *)w, flags, slot, &out->beta_tau_g1));
+  CP_TRY(srs_g1_entry(ctx, out->alpha_tau_g1, 0, out->alpha_g1));
+  CP_TRY(srs_g1_entry(ctx, out->beta_tau_g1, 0, out->beta_g1));
+  return CP_OK;
+}
+
+template <class F>
+int srs_read(cp_ctx *ctx, const void *pts, size_t n, uint64_t *out_host) {
+  if (!out_host) return CP_OK;
+  DevBag tmp = ctx->bag();
+  uint32_t *raw = nullptr;
+  const size_t bytes = n * 2 * bls::Field<F>::WORDS * 4;
+  CP_TRY(alloc_status(ctx, tmp.alloc(&raw, bytes), bytes));
+  LAUNCH(ctx, IS_G1<F> ? "srs_canonical_g1" : "srs_canonical_g2", g16srs::k_canonical<F>, dim3(blocks_for(n, 256)), dim3(256), (const bls::AffineT<F> *)pts, n, raw);
+  HIP_TRY(ctx, hipMemcpyAsync(out_host, raw, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CP_OK;
+}
+
+int groth16_srs_points_run(cp_ctx *ctx, const cp_groth16_srs *srs, int *log_size_out, uint64_t *tau_g1, uint64_t *tau_g2, uint64_t *alpha_tau_g1, uint64_t *beta_tau_g1,
+                           uint64_t *beta_g2) {
+  CP_TRY(srs_on_ctx_device(ctx, srs));
+  const size_t n = (size_t)1 << srs->log_size;
+  CP_TRY(srs_read<bls::Fp>(ctx, srs->tau_g1, 2 * n - 1, tau_g1));
+  CP_TRY(srs_read<bls::Fp2>(ctx, srs->tau_g2, n, tau_g2));
+  CP_TRY(srs_read<bls::Fp>(ctx, srs->alpha_tau_g1, n, alpha_tau_g1));
+  CP_TRY(srs_read<bls::Fp>(ctx, srs->beta_tau_g1, n, beta_tau_g1));
+  if (beta_g2) memcpy(beta_g2, srs->beta_g2, sizeof srs->beta_g2);
+  if (log_size_out) *log_size_out = srs->log_size;
+  return CP_OK;
+}
+
+int srs_verdict(cp_ctx *ctx, int verdict, int *out, const char *why) {
+  (void)set_error(ctx, CP_OK, "SRS check: verdict %d: %s", verdict, why);
+  *out = verdict;
+  return CP_OK;
+}
+
+// L = sum w_k P[k], H = sum w_k P[k + 1] over count adjacent pairs: the same scalars over the array and over the array shifted
+// by one entry; both as affine canonical words with an infinity flag
+template <class F>
+int srs_pair_sums(cp_ctx *ctx, const uint64_t *scalars_dev, const void *pts, size_t count, uint64_t *lo_xy, uint8_t *lo_inf, bool negate_lo, uint64_t *hi_xy, uint8_t *hi_inf,
+                  bool negate_hi) {
+  bls::JacT<F> lo, hi;
+  CP_TRY(msm_run<F>(ctx, (const uint32_t *)scalars_dev, (const bls::AffineT<F> *)pts, nullptr, count, &lo));
+  CP_TRY(msm_run<F>(ctx, (const uint32_t *)scalars_dev, (const bls::AffineT<F> *)pts + 1, nullptr, count, &hi));
+  int inf = 0;
+  jac_out<F>(negate_lo ? bls::jac_neg(lo) : lo, lo_xy, &inf);
+  *lo_inf = (uint8_t)inf;
+  jac_out<F>(negate_hi ? bls::jac_neg(hi) : hi, hi_xy, &inf);
+  *hi_inf = (uint8_t)inf;
+  return CP_OK;
+}
+
+int groth16_srs_check_run(cp_ctx *ctx, const cp_groth16_srs *srs, const uint64_t *weights, int *verdict) {
+  CP_TRY(srs_on_ctx_device(ctx, srs));
+  const size_t n = (size_t)1 << srs->log_size, count = 5 * n - 5;
+  for (size_t i = 0; i < count; i++)
+    if (!(weights[2 * i] | weights[2 * i + 1])) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS check: weight %zu is zero", i);
+  std::vector<uint64_t> scalars(4 * count, 0);
+  for (size_t i = 0; i < count; i++) {
+    scalars[4 * i] = weights[2 * i];
+    scalars[4 * i + 1] = weights[2 * i + 1];
+  }
+  DevBag tmp = ctx->bag();
+  uint64_t *d_scalars = nullptr;
+  CP_TRY(alloc_status(ctx, tmp.alloc(&d_scalars, count * 32), count * 32));
+  HIP_TRY(ctx, hipMemcpyAsync(d_scalars, scalars.data(), count * 32, hipMemcpyHostToDevice, ctx->stream));
+  // product i is pairs 2 i and 2 i + 1; every equation e(X, Y) = e(X', Y') as e(X, Y) e(-X', Y') = 1
+  uint64_t g1[10][12], g2[10][24];
+  uint8_t g1_inf[10] = {}, g2_inf[10] = {}, is_one[5] = {}, status[5] = {};
+  uint64_t neg_gen[12], t1[12], t2[24];
+  {
+    bls::Jac g;
+    int inf = 0;
+    CP_TRY(point_in<bls::Fp>(ctx, BLS_G1_GEN, "the G1 generator", &g));
+    jac_out<bls::Fp>(bls::jac_neg(g), neg_gen, &inf);
+    CP_TRY(srs_g1_entry(ctx, srs->tau_g1, 1, t1));
+    bls::Affine2 q;
+    HIP_TRY(ctx, hipMemcpyAsync(&q, (const bls::Affine2 *)srs->tau_g2 + 1, sizeof q, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t cw[48];
+    bls::Field<bls::Fp2>::to_canonical(q.x, cw);
+    bls::Field<bls::Fp2>::to_canonical(q.y, cw + 24);
+    memcpy(t2, cw, sizeof cw);
+  }
+  const uint64_t *rho = d_scalars, *sigma = rho + 4 * (2 * n - 2), *rho_a = sigma + 4 * (n - 1), *rho_b = rho_a + 4 * (n - 1);
+  // rows 1, 3, 4: e(H(P), G2) e(-L(P), tau_g2[1]) = 1
+  struct Row1 { int product; const uint64_t *w; const void *pts; size_t pairs; } rows[] = {
+      {0, rho, srs->tau_g1, 2 * n - 2}, {2, rho_a, srs->alpha_tau_g1, n - 1}, {3, rho_b, srs->beta_tau_g1, n - 1}};
+  for (const Row1 &r : rows) {
+    const int h = 2 * r.product, l = h + 1;
+    CP_TRY(srs_pair_sums<bls::Fp>(ctx, r.w, r.pts, r.pairs, g1[l], &g1_inf[l], true, g1[h], &g1_inf[h], false));
+    memcpy(g2[h], BLS_G2_GEN, sizeof g2[h]);
+    memcpy(g2[l], t2, sizeof g2[l]);
+  }
+  // row 2: e(tau_g1[1], L(tau_g2)) e(-G1, H(tau_g2)) = 1
+  CP_TRY(srs_pair_sums<bls::Fp2>(ctx, sigma, srs->tau_g2, n - 1, g2[2], &g2_inf[2], false, g2[3], &g2_inf[3], false));
+  memcpy(g1[2], t1, sizeof g1[2]);
+  memcpy(g1[3], neg_gen, sizeof g1[3]);
+  // row 5: e(beta_tau_g1[0], G2) e(-G1, beta_g2) = 1
+  memcpy(g1[8], srs->beta_g1, sizeof g1[8]);
+  memcpy(g2[8], BLS_G2_GEN, sizeof g2[8]);
+  memcpy(g1[9], neg_gen, sizeof g1[9]);
+  memcpy(g2[9], srs->beta_g2, sizeof g2[9]);
+  CP_TRY(cp_pairing_product_bls12381(ctx, &g1[0][0], g1_inf, &g2[0][0], g2_inf, 5, 2, 0, nullptr, is_one, status));
+  for (int i = 0; i < 5; i++)
+    if (status[i] == 3)
+      return srs_verdict(ctx, 6, verdict,
+                         "a combination of the SRS's points is outside the r-torsion: create the SRS with CP_GROTH16_SRS_CHECK_TORSION to find the point");
+  for (int i = 0; i < 5; i++)
+    if (status[i] != 0) return set_error(ctx, CP_ERR_INTERNAL, "SRS check: the pairing call refused product %d with status %d", i, (int)status[i]);
+  static const char *const why[5] = {
+      "e(H(tau_g1), G2) != e(L(tau_g1), tau_g2[1]): tau_g1 is not the powers of the tau of tau_g2[1]",
+      "e(tau_g1[1], L(tau_g2)) != e(G1, H(tau_g2)): tau_g2 is not the powers of the tau of tau_g1[1]",
+      "e(H(alpha_tau_g1), G2) != e(L(alpha_tau_g1), tau_g2[1]): alpha_tau_g1 is not one alpha times the powers of tau",
+      "e(H(beta_tau_g1), G2) != e(L(beta_tau_g1), tau_g2[1]): beta_tau_g1 is not one beta times the powers of tau",
+      "e(beta_tau_g1[0], G2) != e(G1, beta_g2): beta_g2 is not the beta of beta_tau_g1"};
+  for (int i = 0; i < 5; i++)
+    if (!is_one[i]) return srs_verdict(ctx, i + 1, verdict, why[i]);
+  return srs_verdict(ctx, 0, verdict, "the arrays are the powers of one tau, one alpha and one beta times them, and [beta]_2 of the same beta");
+}
+
 }  // namespace
 
 extern "C" {
@@ -564,6 +784,46 @@ int cp_groth16_key_check_contribution_bls12381(cp_ctx *ctx, const cp_groth16_key
   if (!before || !after || !verdict_out) return set_error(ctx, CP_ERR_INVALID_ARG, "contribution check: NULL argument");
   if (!weights_host) return set_error(ctx, CP_ERR_INVALID_ARG, "contribution check: weights is NULL");
   return groth16_check_contribution_run(ctx, before, after, weights_host, verdict_out);
+} CP_CATCH(ctx)
+
+cp_groth16_srs *cp_groth16_srs_unit_bls12381(cp_ctx *ctx, int log_size) try {
+  if (!ctx) { set_error(nullptr, CP_ERR_INVALID_ARG, "ctx is NULL"); return nullptr; }
+  if (hipSetDevice(ctx->device) != hipSuccess) { set_error(ctx, CP_ERR_HIP, "hipSetDevice failed"); return nullptr; }
+  cp_groth16_srs *srs = new cp_groth16_srs(ctx->device);
+  struct Guard { cp_groth16_srs *s; ~Guard() { groth16_srs_free(s); } } guard{srs};
+  if (groth16_srs_unit_run(ctx, log_size, srs) != CP_OK) return nullptr;
+  guard.s = nullptr;
+  return srs;
+} catch (...) {
+  exception_status(ctx);
+  return nullptr;
+}
+
+int cp_groth16_srs_contribute_bls12381(cp_ctx *ctx, const cp_groth16_srs *srs, const uint64_t t[4], const uint64_t a[4], const uint64_t b[4],
+                                       cp_groth16_srs **srs_out) try {
+  CHECK_CTX(ctx);
+  if (srs_out) *srs_out = nullptr;
+  if (!srs || !t || !a || !b || !srs_out) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS contribution: NULL argument");
+  cp_groth16_srs *out = new cp_groth16_srs(ctx->device);
+  struct Guard { cp_groth16_srs *s; ~Guard() { groth16_srs_free(s); } } guard{out};
+  CP_TRY(groth16_srs_contribute_run(ctx, srs, t, a, b, out));
+  guard.s = nullptr;
+  *srs_out = out;
+  return CP_OK;
+} CP_CATCH(ctx)
+
+int cp_groth16_srs_points_bls12381(cp_ctx *ctx, const cp_groth16_srs *srs, int *log_size_out, uint64_t *tau_g1_out, uint64_t *tau_g2_out, uint64_t *alpha_tau_g1_out,
+                                   uint64_t *beta_tau_g1_out, uint64_t beta_g2_out[24]) try {
+  CHECK_CTX(ctx);
+  if (!srs) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS points: the SRS is NULL");
+  return groth16_srs_points_run(ctx, srs, log_size_out, tau_g1_out, tau_g2_out, alpha_tau_g1_out, beta_tau_g1_out, beta_g2_out);
+} CP_CATCH(ctx)
+
+int cp_groth16_srs_check_bls12381(cp_ctx *ctx, const cp_groth16_srs *srs, const uint64_t *weights_host, int *verdict_out) try {
+  CHECK_CTX(ctx);
+  if (!srs || !verdict_out) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS check: NULL argument");
+  if (!weights_host) return set_error(ctx, CP_ERR_INVALID_ARG, "SRS check: weights is NULL");
+  return groth16_srs_check_run(ctx, srs, weights_host, verdict_out);
 } CP_CATCH(ctx)
 
 }  // extern "C"

@@ -1211,9 +1211,10 @@ int cp_point_ntt_bls12381_g2_dev(cp_ctx *ctx, void *points_mont_dev, uint8_t *po
  * srs_create: host arrays, affine canonical (12 u64 per G1 point, 24 per G2 point), copied and converted to the internal
  * form. Every coordinate is checked to be canonical and every point to be on the curve / twist; with
  * CP_GROTH16_SRS_CHECK_TORSION also [r]P = infinity. The first refused point is named by array and index. tau_g1[0] and
- * tau_g2[0] must be the standard generators. NOT checked: that the arrays are consistent with one another - that they are
- * the powers of one tau, and alpha / beta times them. That takes pairings against the ceremony's transcript and is the
- * ceremony's to verify; an SRS is taken as given, like a key file. A key from an inconsistent SRS proves nothing. The handle
+ * tau_g2[0] must be the standard generators. NOT checked here: that the arrays are consistent with one another - that they
+ * are the powers of one tau, and alpha / beta times them. cp_groth16_srs_check_bls12381 (below) checks exactly that, under
+ * weights of the caller; run it on an SRS from outside, for a key from an inconsistent SRS proves nothing. Neither call can
+ * tell whether anybody knows tau: that is the ceremony's transcript, and the ceremony's to verify. The handle
  * lives on the context's device, serves any context of that device and may be destroyed after it; NULL is a no-op.
  *
  * setup_srs: every refusal cp_groth16_setup_bls12381 makes of the system and of n_public, in its words (the private wire
@@ -1253,6 +1254,60 @@ int cp_groth16_key_contribute_bls12381(cp_ctx *ctx, const cp_groth16_key *key, c
                                        cp_groth16_key **key_out);
 int cp_groth16_key_check_contribution_bls12381(cp_ctx *ctx, const cp_groth16_key *before, const cp_groth16_key *after,
                                                const uint64_t *weights_host, int *verdict_out);
+
+/* ---- Phase 1 on the device: make, extend, read back and check a powers-of-tau SRS ----
+ * n = 2^L, L the SRS's log_size. The library draws no randomness, here as everywhere in this ABI: every scalar and every
+ * weight below is the caller's.
+ *
+ * srs_unit: the SRS of tau = alpha = beta = 1: every entry of tau_g1 (2n - 1), alpha_tau_g1 and beta_tau_g1 (n each) is the
+ * standard generator of G1, every entry of tau_g2 (n) and beta_g2 the generator of G2, filled on the device. It is the START
+ * of a ceremony and worthless as an SRS: everybody knows its trapdoor. log_size outside 1 .. 28 is refused. NULL on refusal.
+ *
+ * srs_contribute: *srs_out is a new SRS on the same device; the input is not modified.
+ *     tau_g1'[k] = t^k tau_g1[k] (k < 2n - 1)          tau_g2'[k] = t^k tau_g2[k] (k < n)
+ *     alpha_tau_g1'[k] = a t^k alpha_tau_g1[k]         beta_tau_g1'[k] = b t^k beta_tau_g1[k]         beta_g2' = b beta_g2
+ * Entry 0 of tau_g1 and tau_g2 stays the generator. Applied to the unit SRS it yields the SRS of (t, a, b): one entry point
+ * is the ceremony step and the SRS generator of tests and benchmarks. t, a, b: canonical and not zero, the caller's and the
+ * caller's to destroy; the message names the scalar that is refused. Also refused: a NULL argument, an SRS on another
+ * device, and a result that is the point at infinity (only an input point outside the r-torsion gives one; the message
+ * names the array and the lowest index). *srs_out is NULL after a refusal. 5n - 1 scalar multiplications of 255 bits, each
+ * point under its own scalar c t^k, made on the device.
+ *
+ * srs_points: the SRS as host arrays of affine canonical words in the layout of cp_groth16_srs_desc: tau_g1_out
+ * (2n - 1) x 12 u64, tau_g2_out n x 24, alpha_tau_g1_out and beta_tau_g1_out n x 12, beta_g2_out 24. Any out pointer may be
+ * NULL (not written): a call with log_size_out alone sizes the buffers. What a party publishes, and what srs_create takes.
+ *
+ * srs_check: that the arrays belong together. weights_host: (5n - 5) x 2 u64, a non-zero 128-bit value per ADJACENT PAIR of
+ * entries, little-endian words, in this order: tau_g1 pairs k = 0 .. 2n - 3 (rho), tau_g2 pairs k = 0 .. n - 2 (sigma),
+ * alpha_tau_g1 pairs k = 0 .. n - 2 (rho^a), beta_tau_g1 pairs k = 0 .. n - 2 (rho^b). With the convention and the warning
+ * of cp_groth16_verify_all_bls12381: the weights MUST be unpredictable to whoever made the SRS (fresh output of a
+ * cryptographic generator, drawn after the SRS is fixed); an SRS accepted under predictable weights proves nothing.
+ * For an array P with weights w: L(P) = sum_k w_k P[k], H(P) = sum_k w_k P[k + 1]. *verdict_out is 0, or the first row that
+ * fails:
+ *     1   e(H(tau_g1), G2)       = e(L(tau_g1), tau_g2[1])
+ *     2   e(tau_g1[1], L(tau_g2)) = e(G1, H(tau_g2))
+ *     3   e(H(alpha_tau_g1), G2) = e(L(alpha_tau_g1), tau_g2[1])
+ *     4   e(H(beta_tau_g1), G2)  = e(L(beta_tau_g1), tau_g2[1])
+ *     5   e(beta_tau_g1[0], G2)  = e(G1, beta_g2)
+ *     6   a combination of the points is outside the r-torsion (status 3 of cp_pairing_product_bls12381; it comes before
+ *         the rows): create the SRS with CP_GROTH16_SRS_CHECK_TORSION to find the point
+ * srs_create pins tau_g1[0] and tau_g2[0] to the generators; with that, verdict 0 means that the arrays are the powers of one
+ * tau, one alpha and one beta times them, and [beta]_2 of the same beta, up to an error of 2^-128 per pair. The call
+ * returns CP_OK whatever the verdict and cp_last_error carries the reason; CP_ERR_INVALID_ARG for a NULL argument, an SRS
+ * on another device and a weight of zero (the message names its index). Six MSMs in G1, two in G2, one pairing call of five
+ * products of two pairs.
+ * What the check does NOT establish: that tau is unknown to anybody (the unit SRS passes); that a contributor knew its t;
+ * that one SRS was built on another. The last two are a proof of knowledge and a transcript: the ceremony's protocol layer,
+ * which stays with the caller as it does for the delta contributions. There is no check_contribution for phase 1: from two
+ * SRS alone, a step is valid exactly when its result is consistent.
+ * A refused allocation is CP_ERR_OOM in all four (NULL from srs_unit); the context stays usable and nothing is held. */
+cp_groth16_srs *cp_groth16_srs_unit_bls12381(cp_ctx *ctx, int log_size);
+int cp_groth16_srs_contribute_bls12381(cp_ctx *ctx, const cp_groth16_srs *srs, const uint64_t t[4], const uint64_t a[4],
+                                       const uint64_t b[4], cp_groth16_srs **srs_out);
+int cp_groth16_srs_points_bls12381(cp_ctx *ctx, const cp_groth16_srs *srs, int *log_size_out, uint64_t *tau_g1_out,
+                                   uint64_t *tau_g2_out, uint64_t *alpha_tau_g1_out, uint64_t *beta_tau_g1_out,
+                                   uint64_t beta_g2_out[24]);
+int cp_groth16_srs_check_bls12381(cp_ctx *ctx, const cp_groth16_srs *srs, const uint64_t *weights_host, int *verdict_out);
 
 #ifdef __cplusplus
 }

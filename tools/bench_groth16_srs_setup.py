@@ -4,8 +4,9 @@ beside the trapdoor setup at the same size, on tests/r1cs_cases.satisfied_system
 tests/test_gpu_groth16_srs_setup.py and tests/test_gpu_groth16_contribute.py; this measures - but at every size the bytes of the
 SRS key are compared with the trapdoor key's (gamma = delta = 1) before anything is reported. The issue that asked for this path
 sets no time bound: the figures are a record, not a check. In one process, per size:
-  srs_build_s            the SRS from a known tau with the fixed-base multiplication, read back to host arrays (Python integer
-                         arithmetic per point: the slowest step of this tool, not part of the library), and cp_groth16_srs_create
+  srs_build_s            the SRS of a known (tau, alpha, beta) made on the device: cp_groth16_srs_unit_bls12381, then
+                         cp_groth16_srs_contribute_bls12381 (tests/test_gpu_groth16_srs_phase1.py holds that pair, word for word,
+                         against the fixed-base multiples this tool used to read back through Python integers)
   srs_setup              wall_ms: host clock around one call after one warm-up call. phases_ms: one further call under
                          cp_profile_begin / cp_profile_end, the host clock of each phase (a phase ends with a stream
                          synchronisation, so its clock holds its kernels): point_ntts (the four inverse transforms), columns (the
@@ -47,7 +48,11 @@ def run(prover, log_n, n_public=16):
     coeffs = RC.limbs4(s["coeffs"])
     L = GC.log_domain(s["n"])
     t0 = time.perf_counter()
-    srs = SC.make_srs(prover, SC.srs_arrays(prover, td, L))
+    unit = cp.Groth16Srs.unit(prover, L)
+    try:
+        srs = unit.contribute(td["tau"], td["alpha"], td["beta"])
+    finally:
+        unit.free()
     srs_build_s = time.perf_counter() - t0
 
     def from_srs():
