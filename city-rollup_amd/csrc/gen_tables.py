@@ -216,6 +216,30 @@ def perm_fast(s, RC, tabs):
     return s
 
 
+# limbs that `recombine_s` (poseidon.h) takes, as closed integer ranges. A full-round layer multiplies non-negative 32-bit limbs by
+# the circulant (entries sum to 256) plus the diagonal 8; the partial rounds hand over whatever the limb -> integer conversion holds:
+# the mantissa of limb + 1.5 * 2^52 is limb + 2^51 >= 0, and `recombine_d` states |limb| < 2^51 - 2^32.
+FULL_LIMBS = (0, 264 * 0xFFFFFFFF)
+PARTIAL_LIMBS = (-(1 << 51), (1 << 51) - (1 << 32) - 1)
+TOP_MAX = 1 << 20     # what the top word of `recombine_s` may reach (a wrap of the fold then cannot happen twice)
+
+
+def top0_margin(limbs):
+    """the smallest margin m with m + floor((h + c1) / 2^32) + carry >= 0 for every high limb h of the range, every half c1 of a
+    constant (0 <= c1 < 2^32) and carry in {0, 1}; checks that the same sum stays within TOP_MAX"""
+    lo, hi = limbs
+    m = max(0, -(lo >> 32))
+    assert m + ((hi + 0xFFFFFFFF) >> 32) + 1 <= TOP_MAX
+    return m
+
+
+def top0_literals():
+    """name -> the literal `recombine_s` subtracts from the top word: the high word of the magic constant's bit pattern (1.5 * 2^52
+    in units of 1, 1.5 * 2^20 in units of 2^32) minus the margin of the limbs it meets"""
+    bhi, bhi32 = ((0x433 << 52) + (1 << 51)) >> 32, ((0x413 << 52) + (1 << 51)) >> 32
+    return {"FULL": bhi - top0_margin(FULL_LIMBS), "PARTIAL": bhi - top0_margin(PARTIAL_LIMBS), "PARTIAL32": bhi32 - top0_margin(PARTIAL_LIMBS)}
+
+
 def c_array(name, vals, per_line=4, ctype="uint64_t", qualifier="const"):
     body = ""
     for i in range(0, len(vals), per_line):
@@ -293,6 +317,22 @@ def main():
     out += "// the same for planes in units of 2^32: 1.5 * 2^20 + lo32 * 2^-32 and 1.5 * 2^20 + hi32 * 2^-32, constants minus that pattern\n"
     out += c_array("POSEIDON_DOMD32_K", magic32_pairs([(k - biasd32) % P for k in DK]))
     out += c_array("POSEIDON_DOMD32_LAST", magic32_pairs([(k - biasd32) % P for k in DLAST]))
+    # The recombination with a SMALL top word (poseidon.h `recombine_s`): the top word of the sum of the two bit patterns carries
+    # the exponent pattern Bhi = B >> 32 of the magic constant. The device subtracts the literal T0 = Bhi - margin from it, which
+    # leaves margin + (the data-dependent part) — a few bits, so that the fold top * (2^32 - 1) almost never wraps 2^64 — and what
+    # went away, T0 * 2^64 == T0 * (2^32 - 1), is put back into the constants. The margins come from the bounds of the limbs:
+    #   full-round layers (units of 1): limbs are sums of non-negative products, 0 <= h <= 264 (2^32 - 1): margin 0;
+    #   partial rounds (either unit): |l|, |h| < 2^51 - 2^32, what `recombine_d` converts: floor((h + c1) / 2^32) >= -2^19: margin 2^19.
+    out += "// the same three families for `recombine_s`: the literal POSEIDON_TOP0_* is subtracted from the top word and put back here\n"
+    top0 = top0_literals()
+    for name, v in top0.items():
+        out += f"constexpr uint32_t POSEIDON_TOP0_{name} = 0x{v:08x}u;\n"
+    back = {k: v * 0xFFFFFFFF % P for k, v in top0.items()}
+    out += c_array("POSEIDON_RCS", magic_pairs([(k - biasd + back["FULL"]) % P for k in RC] + [(back["FULL"] - biasd) % P]), qualifier="constexpr")
+    out += c_array("POSEIDON_DOMS_K", magic_pairs([(k - biasd + back["PARTIAL"]) % P for k in DK]), qualifier="constexpr")
+    out += c_array("POSEIDON_DOMS_LAST", magic_pairs([(k - biasd + back["PARTIAL"]) % P for k in DLAST]), qualifier="constexpr")
+    out += c_array("POSEIDON_DOMS32_K", magic32_pairs([(k - biasd32 + back["PARTIAL32"]) % P for k in DK]), qualifier="constexpr")
+    out += c_array("POSEIDON_DOMS32_LAST", magic32_pairs([(k - biasd32 + back["PARTIAL32"]) % P for k in DLAST]), qualifier="constexpr")
     out += "// round 0 of a capacity word that is zero on entry (poseidon.h `ZERO_CAP`): (0 + RC[8 + i])^7, canonical\n"
     out += c_array("POSEIDON_CAP0_SBOX", [pow(RC[8 + i], 7, P) for i in range(4)], qualifier="constexpr")
     out += "// primitive 2^k-th roots of unity, k = 0..32 (7^((p-1)/2^k))\n"

@@ -101,6 +101,35 @@ GL_HD uint64_t fold_top(uint64_t lo, uint32_t top) {
 #endif
 }
 
+// The same fold for a caller that knows its top word SMALL (top <= 2^20: poseidon.h `recombine_s`), in two halves. The sum wraps 2^64
+// only when the 64 - 20 - 32 = 12 high bits of `lo` are all ones, so the repair is taken out of the stream: `fold_top_open` is the
+// multiply-add alone — it returns the sum mod 2^64 and leaves the wrap in `wrap` (device: the SGPR pair the instruction wrote its
+// carry-out to, one bit per lane; host: 0 or 1) — and the caller ORs the wraps of as many folds as it likes on the scalar side, tests
+// the union once and, behind that wave-uniform branch, hands every sum and its own wrap to `fold_repair` (+ EPS where the bit is
+// set, nothing where it is not). One wrap suffices: lo + top (2^32 - 1) < 2^64 + 2^52, so a wrapped sum is below 2^52 and + EPS
+// cannot wrap it again. fold_repair(fold_top_open(lo, top, w), w) == fold_top(lo, top), bit for bit.
+GL_HD uint64_t fold_top_open(uint64_t lo, uint32_t top, uint64_t &wrap) {
+#if GL_DEVICE_ASM
+  uint64_t r;
+  asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=&v"(r), "=&s"(wrap) : "v"(top), "v"(lo));
+  return r;
+#else
+  const u128 s = (u128)lo + (((uint64_t)top << 32) - top);
+  wrap = (uint64_t)(s >> 64);
+  return (uint64_t)s;
+#endif
+}
+GL_HD uint64_t fold_repair(uint64_t r, uint64_t wrap) {
+#if GL_DEVICE_ASM
+  // `wrap` was written by a VALU instruction of another statement: the two wait states in front of the read (see above)
+  uint32_t m;
+  asm volatile("s_nop 1\n\tv_cndmask_b32 %0, 0, -1, %1" : "=v"(m) : "s"(wrap));
+  return r + m;
+#else
+  return r + ((0 - wrap) & EPS);
+#endif
+}
+
 // 128-bit (hi:lo) -> lazy u64 (any representative):  lo - hi_hi + hi_lo*(2^32-1),
 // every wrap of 2^64 repaid by -+EPS
 GL_HD uint64_t reduce128_lazy(uint64_t lo, uint64_t hi) {

@@ -44,6 +44,8 @@ GL_HD uint64_t rc(int i) {
 // positions, as the two doubles 1.5 * 2^52 + lo32 and 1.5 * 2^52 + hi32 — added to a limb they convert it to an integer AND
 // add the constant in one operation. RCD = the round constants (+ one entry for "no constant"); DDK / DDLAST = the partial-round constants pushed
 // forward through the MDS (gen_tables.plane_constants: one scalar per partial round on element 0, one vector after the last).
+// Hosts upload all three; only the forms kept for the A/B read them (POSEIDON_RECOMBINE_V1, POSEIDON_PARTIAL_V1): the default build
+// takes the tables of `recombine_s` below.
 struct Magic { double m0, m1; };
 __constant__ uint64_t d_RCD[2 * (ROUNDS * W + 1)];
 __constant__ uint64_t d_DDK[2 * PARTIAL];
@@ -80,6 +82,24 @@ GL_HD Magic domd_last(int i) {
 #else
   return {__builtin_bit_cast(double, DDLAST_HOST[2 * i]), __builtin_bit_cast(double, DDLAST_HOST[2 * i + 1])};
 #endif
+}
+// The constants of `recombine_s` (below `recombine_d`): the same three families with T0 * (2^32 - 1) put back for the literal T0 that
+// the recombination takes off its top word (gen_tables.top0_literals). They are compile-time tables of the header, read in place (a
+// uniform index: scalar loads) — no host uploads them. POSEIDON_RECOMBINE_V1: `recombine_d` and its tables everywhere, kept for the A/B.
+#if defined(POSEIDON_RECOMBINE_V1)
+constexpr bool SMALL_TOP = false;
+#else
+constexpr bool SMALL_TOP = true;
+#endif
+constexpr uint32_t TOP0_PLANES = UNITS32 ? POSEIDON_TOP0_PARTIAL32 : POSEIDON_TOP0_PARTIAL;
+GL_HD Magic rcs(int i) { return {__builtin_bit_cast(double, POSEIDON_RCS[2 * i]), __builtin_bit_cast(double, POSEIDON_RCS[2 * i + 1])}; }
+GL_HD Magic doms_k(int i) {
+  const uint64_t(&t)[2 * PARTIAL] = UNITS32 ? POSEIDON_DOMS32_K : POSEIDON_DOMS_K;
+  return {__builtin_bit_cast(double, t[2 * i]), __builtin_bit_cast(double, t[2 * i + 1])};
+}
+GL_HD Magic doms_last(int i) {
+  const uint64_t(&t)[2 * W] = UNITS32 ? POSEIDON_DOMS32_LAST : POSEIDON_DOMS_LAST;
+  return {__builtin_bit_cast(double, t[2 * i]), __builtin_bit_cast(double, t[2 * i + 1])};
 }
 // ---- what a caller keeps of a permutation, and what it knows of its input --------------------------------------------------
 // `hash_no_pad` is an overwrite-mode sponge: the rate words 0..7 of every permutation but a leaf's last are overwritten by the
@@ -353,6 +373,59 @@ GL_HD uint64_t recombine_d(double l, double h, Magic m) {
   const uint32_t carry = __builtin_add_overflow(gl::hi32(a0), gl::lo32(a1), &w1);
   return fold_top(gl::pack(gl::lo32(a0), w1), gl::hi32(a1) + carry);
 }
+// The same with a SMALL top word, and the rare wrap of its fold left to the caller. In `recombine_d` the top word hi32(a1) + carry is
+// Bhi + floor(x1 / 2^32) + carry with Bhi = B >> 32 (0x43380000; 0x41380000 for planes in units of 2^32) and x1 = h + hi32(c'): about
+// 2^30 whatever the data, so `fold_top` wraps 2^64 every fourth time and pays a select and an add on every call. Here the literal
+// T0 = Bhi - margin is taken off the top word as it is formed (two instructions as before), and the constants `m` come from the tables
+// that have T0 2^64 == T0 (2^32 - 1) put back (POSEIDON_RCS / DOMS*_K / DOMS*_LAST with POSEIDON_TOP0_FULL / _PARTIAL / _PARTIAL32).
+//   * top >= 0 for every reachable (l, h), negative limbs included. The bit pattern of 1.5 * 2^52 + x is the integer B + x for
+//     -2^51 <= x < 2^51: the mantissa field holds 2^51 + x >= 0, the exponent field does not move. So a1 = B + x1 with the low word of B
+//     zero, hi32(a1) = Bhi + floor(x1 / 2^32) (floor towards -infinity), and top = margin + floor(x1 / 2^32) + carry. A NEGATIVE h only
+//     lowers that floor, to no less than -2^19 (h >= -2^51, hi32(c') >= 0), which the margin 2^19 of the partial rounds covers; in a
+//     full-round layer h >= 0 and the margin is 0. The sign of l does not enter: hi32(a0) = Bhi + floor(x0 / 2^32) is added to lo32(a1)
+//     mod 2^32 and its carry counted, so lo + 2^64 (hi32(a1) + carry) is a0 + 2^32 a1 exactly, whatever the signs.
+//   * top <= 2^20: floor(x1 / 2^32) <= 2^19 - 1 for h < 2^51 - 2^32, plus the carry, plus the margin (gen_tables.top0_margin asserts it).
+//   * one wrap suffices: lo + top (2^32 - 1) < 2^64 + 2^52, so a wrapped sum is below 2^52 and + EPS does not wrap it (gl::fold_top_open).
+// The result is the one of `recombine_d` on the same value up to a multiple of p: another lazy representative of the same residue.
+// `wrap` must go to gl::fold_repair with the result whenever it is non-zero (`repair_s`); a caller ORs several and tests once.
+template <uint32_t T0>
+GL_HD uint64_t recombine_s(double l, double h, Magic m, uint64_t &wrap) {
+  const uint64_t a0 = __builtin_bit_cast(uint64_t, l + m.m0), a1 = __builtin_bit_cast(uint64_t, h + m.m1);
+  // middle and top word in one 64-bit sum, d = a1 + hi32(a0) (no wrap: a1 < 2^63): hi32(d) is hi32(a1) + carry. As a multiply-add by 1
+  // it is one instruction that leaves VCC alone, and the literal then rides a plain 32-bit add — an add with carry-in cannot take a
+  // literal on gfx9 (one constant-bus read), and a register that holds it is one the leaf hash does not have.
+#if GL_DEVICE_ASM
+  uint64_t d, unused;
+  asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=&v"(d), "=&s"(unused) : "v"(gl::hi32(a0)), "v"(a1));
+#else
+  const uint64_t d = a1 + gl::hi32(a0);
+#endif
+  return gl::fold_top_open(gl::pack(gl::lo32(a0), gl::lo32(d)), gl::hi32(d) - T0, wrap);
+}
+// A test build counts the repairs per site (0: a full-round layer, 1: one partial round, 2: the exit of the partial rounds).
+#if !defined(POSEIDON_WRAP_PROBE)
+#define POSEIDON_WRAP_PROBE(site) ((void)0)
+#endif
+// the rare path of N recombinations, behind ONE test of the union of their wraps (wave-uniform on the device: SGPR pairs)
+template <int N>
+GL_HD void repair_s(uint64_t *r, const uint64_t (&wrap)[N], int site) {
+  uint64_t any = wrap[0];
+#pragma unroll
+  for (int i = 1; i < N; i++) any |= wrap[i];
+  if (__builtin_expect(any != 0, 0)) {
+    POSEIDON_WRAP_PROBE(site);
+#pragma unroll
+    for (int i = 0; i < N; i++) r[i] = gl::fold_repair(r[i], wrap[i]);
+  }
+}
+// the N recombinations of a layer or an exit: all wraps ORed, one test (`c(i)`: the constant of word i; smaller groups: DESIGN.md §4.1 (8))
+template <uint32_t T0, int N, typename Const>
+GL_HD void recombine_all_s(const double (&yl)[N], const double (&yh)[N], Const c, uint64_t *r, int site) {
+  uint64_t wrap[N];
+#pragma unroll
+  for (int i = 0; i < N; i++) r[i] = recombine_s<T0>(yl[i], yh[i], c(i), wrap[i]);
+  repair_s(r, wrap, site);
+}
 
 // the butterflies back for the live words only: y[0..3] = words 0..3 (digest) or words 8..11 (capacity)
 GL_HD void dom_leave_digest_d(const double (&o)[W], double (&y)[4]) {
@@ -382,8 +455,12 @@ GL_HD void mds_layer_d(uint64_t (&s)[W], int next_rc_base) {
   dom_mul_d<false>(u, o);
   dom_leave_d(o, yh);
   yh[0] = __builtin_fma(lh[0], 8.0, yh[0]);
+  if (SMALL_TOP) {
+    recombine_all_s<POSEIDON_TOP0_FULL>(yl, yh, [&](int i) { return rcs(next_rc_base >= 0 ? next_rc_base + i : ROUNDS * W); }, s, 0);
+  } else {
 #pragma unroll
-  for (int i = 0; i < W; i++) s[i] = recombine_d(yl[i], yh[i], rcd(next_rc_base >= 0 ? next_rc_base + i : ROUNDS * W));
+    for (int i = 0; i < W; i++) s[i] = recombine_d(yl[i], yh[i], rcd(next_rc_base >= 0 ? next_rc_base + i : ROUNDS * W));
+  }
 }
 // The permutation's LAST layer (no constant follows it) for a form that keeps four words: only those leave the domain and are
 // recombined (the products nobody reads go with them). The dead words are cleared.
@@ -411,13 +488,21 @@ GL_HD void mds_last_layer_d(uint64_t (&s)[W]) {
   } else {
     dom_leave_capacity_d(o, yh);
   }
-  const Magic none = rcd(ROUNDS * W);
+  uint64_t r[4];
+  if (SMALL_TOP) {
+    const Magic none = rcs(ROUNDS * W);
+    recombine_all_s<POSEIDON_TOP0_FULL>(yl, yh, [&](int) { return none; }, r, 0);
+  } else {
+    const Magic none = rcd(ROUNDS * W);
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = recombine_d(yl[i], yh[i], none);
+  }
 #pragma unroll
   for (int i = 0; i < W; i++) s[i] = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    if (DIGEST) s[i] = gl::canon(recombine_d(yl[i], yh[i], none));
-    else s[RATE + i] = recombine_d(yl[i], yh[i], none);
+    if (DIGEST) s[i] = gl::canon(r[i]);
+    else s[RATE + i] = r[i];
   }
 }
 // ---- the scaled layer two deep (partial_rounds): constants derived from dom_mul_d<true> at compile time ------------------------
@@ -438,17 +523,24 @@ constexpr DomMat<6> DOM_K_B = {{{4, 2, 2, -2, -32, 8}, {-8, 4, 2, 2, -2, -32}, {
                                 {2, 32, -8, 4, 2, 2}, {-2, 2, 32, -8, 4, 2}, {-2, -2, 2, 32, -8, 4}}};
 constexpr DomMat<3> DOM_K_AB2 = dom_mat_sq(DOM_K_AB);
 constexpr DomMat<6> DOM_K_B2 = dom_mat_sq(DOM_K_B);
-// l K: element 0 of the NEXT layer read off this layer's inputs (rows 0, 3, 6 of K)
-GL_HD double dom_next_z(const double (&u)[W]) {
-  constexpr double CZ[W] = {64, 64, 128, -4, -8, 32, 4, 2, 2, -2, -32, 8};
+// l K: element 0 of the NEXT layer read off this layer's inputs (rows 0, 3, 6 of K). The aa and ab parts are apart from the b part,
+// which `partial_rounds` takes in another basis (`dom_next_z_b`, `dom_mul2_b` below): one copy of their constants.
+GL_HD double dom_next_z_a(const double (&u)[W]) {
+  constexpr double CZ[6] = {64, 64, 128, -4, -8, 32};
   double acc = u[0] * CZ[0];
 #pragma unroll
-  for (int k = 1; k < W; k++) acc = __builtin_fma(u[k], CZ[k], acc);
+  for (int k = 1; k < 6; k++) acc = __builtin_fma(u[k], CZ[k], acc);
+  return acc;
+}
+GL_HD double dom_next_z(const double (&u)[W]) {
+  double acc = dom_next_z_a(u);
+#pragma unroll
+  for (int k = 0; k < 6; k++) acc = __builtin_fma(u[6 + k], DOM_K_B.a[0][k], acc);
   return acc;
 }
 // o = K^2 u + d K t   (K t = columns 0 of the blocks of K over (4, 4, 2): a change d of element 0, one layer on)
-GL_HD void dom_mul2_d(const double (&u)[W], double d, double (&o)[W]) {
-  constexpr double KT[W] = {16, 32, 16, -1, -8, 2, 2, -4, 16, 1, -1, -1};
+GL_HD void dom_mul2_a(const double (&u)[W], double d, double (&o)[W]) {
+  constexpr double KT[6] = {16, 32, 16, -1, -8, 2};
   // aa: (64 (J + P))^2 = 4096 (5 J + P^2), P^2: row i takes column (i + 1) % 3
   const double t = (u[0] + u[1] + u[2]) * 20480.0;
   o[0] = __builtin_fma(u[1], 4096.0, __builtin_fma(d, KT[0], t));
@@ -461,11 +553,111 @@ GL_HD void dom_mul2_d(const double (&u)[W], double d, double (&o)[W]) {
     for (int j = 0; j < 3; j++) acc = __builtin_fma(u[3 + j], DOM_K_AB2.a[k][j], acc);
     o[3 + k] = acc;
   }
+}
+GL_HD void dom_mul2_d(const double (&u)[W], double d, double (&o)[W]) {
+  dom_mul2_a(u, d, o);
 #pragma unroll
   for (int k = 0; k < 6; k++) {
-    double acc = d * KT[6 + k];
+    double acc = d * (DOM_K_B.a[k][0] / 2);
 #pragma unroll
     for (int j = 0; j < 6; j++) acc = __builtin_fma(u[6 + j], DOM_K_B2.a[k][j], acc);
+    o[6 + k] = acc;
+  }
+}
+
+// ---- the b block in a basis where it is block-triangular (partial_rounds) ------------------------------------------------------------
+// The b block is multiplication by a fixed polynomial in Z[x] / (x^6 + 1), and x^6 + 1 = (x^2 + 1)(x^4 - x^2 + 1). Reduction mod
+// x^4 - x^2 + 1 (x^4 -> x^2 - 1, x^5 -> x^3 - x) is a ring map, so the four coordinates B = (u0 - u4, u1 - u5, u2 + u4, u3 + u5) of
+// u mod (x^4 - x^2 + 1) are mapped among themselves. In the basis (B0, B1, B2, B3, u4, u5) = T u the layer is T K T^-1: integer
+// entries (T and T^-1 are), rows 0..3 with a zero 4 x 2 corner — 28 non-zeros where the dense square has 36, and one more zero in
+// K t. The planes stay in that basis from the entry of `partial_rounds` to its exit (`dom_b_to_tri`, `dom_b_from_tri`: four additions
+// per plane each); the carry normalisation acts per component and commutes with any integer basis change up to multiples of p. What
+// the rounds need in that basis: element 0 reads v0 = B0 + u4, so l = e0 + e3 + e6 + e10; a change of element 0 is d / 2 on v0, and
+// T e0 = e0: it still lands on index 6 alone. Magnitudes: the absolute row sums of (T K T^-1)^2 are at most 3 420 and those of l K
+// there 52 where the dense ones are 50, against 65 536 and 256 for the aa block, which stays the bound of every plane; B2 and B3 are
+// sums of two old components, one more bit, only between the entry's products and the first normalisation and again at the exit,
+// where u2 = B2 - u4 and u3 = B3 - u5 are differences of two b components (each below 2^-4 of an aa component).
+// POSEIDON_BBLOCK_DENSE: the dense block in the old basis, kept for the A/B.
+#if defined(POSEIDON_BBLOCK_DENSE)
+constexpr bool B_TRI = false;
+#else
+constexpr bool B_TRI = true;
+#endif
+template <int N> constexpr DomMat<N> dom_mat_mul(const DomMat<N> &x, const DomMat<N> &y) {
+  DomMat<N> r{};
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j < N; j++) {
+      double acc = 0;
+      for (int k = 0; k < N; k++) acc += x.a[i][k] * y.a[k][j];
+      r.a[i][j] = acc;
+    }
+  return r;
+}
+template <int N> constexpr bool dom_mat_is_identity(const DomMat<N> &m) {
+  for (int i = 0; i < N; i++)
+    for (int j = 0; j < N; j++)
+      if (m.a[i][j] != (i == j ? 1.0 : 0.0)) return false;
+  return true;
+}
+constexpr DomMat<6> DOM_B_T = {{{1, 0, 0, 0, -1, 0}, {0, 1, 0, 0, 0, -1}, {0, 0, 1, 0, 1, 0}, {0, 0, 0, 1, 0, 1}, {0, 0, 0, 0, 1, 0}, {0, 0, 0, 0, 0, 1}}};
+constexpr DomMat<6> DOM_B_TINV = {{{1, 0, 0, 0, 1, 0}, {0, 1, 0, 0, 0, 1}, {0, 0, 1, 0, -1, 0}, {0, 0, 0, 1, 0, -1}, {0, 0, 0, 0, 1, 0}, {0, 0, 0, 0, 0, 1}}};
+static_assert(dom_mat_is_identity(dom_mat_mul(DOM_B_T, DOM_B_TINV)), "T^-1 is the inverse of T");
+constexpr DomMat<6> DOM_K_BT = dom_mat_mul(dom_mat_mul(DOM_B_T, DOM_K_B), DOM_B_TINV);
+constexpr DomMat<6> DOM_K_BT2 = dom_mat_sq(DOM_K_BT);
+template <int N> constexpr bool dom_corner_is_zero(const DomMat<N> &m, int rows, int from) {
+  for (int i = 0; i < rows; i++)
+    for (int j = from; j < N; j++)
+      if (m.a[i][j] != 0.0) return false;
+  return true;
+}
+static_assert(dom_corner_is_zero(DOM_K_BT, 4, 4) && dom_corner_is_zero(DOM_K_BT2, 4, 4), "rows B0..B3 do not read u4, u5");
+// what the rounds read of the b block in the basis they run in: the squared block, the b part of l K (row v0 = B0 + u4 of K) and the
+// b part of K t (column v0 of K over 2: T e0 = e0)
+struct DomVec6 { double a[6]; };
+constexpr DomVec6 dom_b_next_z(bool tri) {
+  DomVec6 r{};
+  for (int j = 0; j < 6; j++) r.a[j] = tri ? DOM_K_BT.a[0][j] + DOM_K_BT.a[4][j] : DOM_K_B.a[0][j];
+  return r;
+}
+constexpr DomVec6 dom_b_kt(bool tri) {
+  DomVec6 r{};
+  for (int i = 0; i < 6; i++) r.a[i] = (tri ? DOM_K_BT.a[i][0] : DOM_K_B.a[i][0]) / 2;
+  return r;
+}
+constexpr DomMat<6> DOM_B2 = B_TRI ? DOM_K_BT2 : DOM_K_B2;
+constexpr DomVec6 DOM_B_CZ = dom_b_next_z(B_TRI), DOM_B_KT = dom_b_kt(B_TRI);
+// products in the old basis -> the basis of the rounds, and back (indices 6..11 of a plane)
+GL_HD void dom_b_to_tri(double (&o)[W]) {
+  o[6] -= o[10], o[7] -= o[11], o[8] += o[10], o[9] += o[11];
+}
+GL_HD void dom_b_from_tri(double (&o)[W]) {
+  o[6] += o[10], o[7] += o[11], o[8] -= o[10], o[9] -= o[11];
+}
+// element 0 read off the products (l W), `dom_next_z` and `dom_mul2_d` with the b block in the basis of the rounds. A zero entry
+// costs nothing: after unrolling, which terms exist is known at compile time (the dense form issues what `dom_mul2_d` issues).
+GL_HD double dom_read_z(const double (&w)[W]) {
+  const double z = w[0] + w[3] + w[6];
+  return B_TRI ? z + w[10] : z;
+}
+GL_HD double dom_next_z_b(const double (&u)[W]) {
+  double acc = dom_next_z_a(u);
+#pragma unroll
+  for (int k = 0; k < 6; k++) acc = __builtin_fma(u[6 + k], DOM_B_CZ.a[k], acc);
+  return acc;
+}
+GL_HD void dom_mul2_b(const double (&u)[W], double d, double (&o)[W]) {
+  dom_mul2_a(u, d, o);
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    double acc = 0;
+    bool first = true;
+    if (DOM_B_KT.a[k] != 0.0) acc = d * DOM_B_KT.a[k], first = false;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      if (DOM_B2.a[k][j] == 0.0) continue;
+      acc = first ? u[6 + j] * DOM_B2.a[k][j] : __builtin_fma(u[6 + j], DOM_B2.a[k][j], acc);
+      first = false;
+    }
     o[6 + k] = acc;
   }
 }
@@ -494,7 +686,7 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
   }
   // From here to the exit the planes are in units of 2^32 (UNITS32; U = 1 restores units of 1). Every operation multiplies by a
   // compile-time constant or adds two planes, so the unit costs nothing: only where a limb of an S-box output (nl, nh: units of 1)
-  // meets a plane does its factor carry U, and `recombine_d` gets the constants of that unit (DDK_HOST / DDLAST_HOST).
+  // meets a plane does its factor carry U, and the recombination gets the constants of that unit (`doms_k` / `doms_last`; `recombine_d`: DDK_HOST / DDLAST_HOST).
   constexpr double U = UNITS32 ? 0x1p-32 : 1.0;
   // TWO partial rounds per trip, with ONE application of the layer squared. Let W = (E, F, v) be the products at the top of round r,
   // K the scaled layer (dom_mul_d<true>), t = (1/4, 0, 0 | 1/4, 0, 0 | 1/2, 0, ...) what a change of element 0 is in the domain and
@@ -540,11 +732,21 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
 #pragma unroll
   for (int k = 0; k < W; k++) s[k] = recombine_d(yl[k], yh[k], domd_last(k));
 #else
+  // The b block of both planes lives in the basis (B0..B3, u4, u5) from here to the exit (B_TRI; see `dom_b_to_tri`).
+  if (B_TRI) dom_b_to_tri(ol), dom_b_to_tri(oh);
+  // element 0 of a round from its limbs: `recombine_s` with its own test of the rare wrap (SMALL_TOP), else `recombine_d`
+  auto element0 = [&](int i, double l, double h) -> uint64_t {
+    if (!SMALL_TOP) return recombine_d(l, h, domd_k(i));
+    uint64_t r[1], wrap[1];
+    r[0] = recombine_s<TOP0_PLANES>(l, h, doms_k(i), wrap[0]);
+    repair_s(r, wrap, 1);
+    return r[0];
+  };
   auto trip = [&](int i, double (&al)[W], double (&ah)[W], double (&bl)[W], double (&bh)[W]) {
     // round i: element 0 = E0 + F0 + v0 + the diagonal 8 of the MDS on the previous S-box output
     {
-      const double zl = al[0] + al[3] + al[6], zh = ah[0] + ah[3] + ah[6];
-      const uint64_t x = sbox_lazy_chain(input(i, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i))));
+      const double zl = dom_read_z(al), zh = dom_read_z(ah);
+      const uint64_t x = sbox_lazy_chain(input(i, element0(i, __builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh))));
       nl = (double)(uint32_t)x;
       nh = (double)(uint32_t)(x >> 32);
       const double dl = __builtin_fma(nl, U, -zl), dh = __builtin_fma(nh, U, -zh);
@@ -555,15 +757,15 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
 #pragma unroll
     for (int k = 0; k < W; k++) renorm_planes_d(al[k], ah[k]);
     // round i + 1: element 0 one layer ahead, then the squared layer with the change of element 0 carried one layer on (a -> b)
-    const double zl = dom_next_z(al), zh = dom_next_z(ah);
-    const uint64_t x = sbox_lazy_chain(input(i + 1, recombine_d(__builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh), domd_k(i + 1))));
+    const double zl = dom_next_z_b(al), zh = dom_next_z_b(ah);
+    const uint64_t x = sbox_lazy_chain(input(i + 1, element0(i + 1, __builtin_fma(nl, 8.0 * U, zl), __builtin_fma(nh, 8.0 * U, zh))));
     nl = (double)(uint32_t)x;
     nh = (double)(uint32_t)(x >> 32);
-    dom_mul2_d(al, __builtin_fma(nl, U, -zl), bl);
+    dom_mul2_b(al, __builtin_fma(nl, U, -zl), bl);
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(POSEIDON_INTERLEAVE_PLANES)  // the macro: A/B in tools/ubench_leaf_residency.hip
     __builtin_amdgcn_sched_barrier(0);  // one plane after the other: interleaved, the four arrays are live at once and the leaf hash (96 registers) spills
 #endif
-    dom_mul2_d(ah, __builtin_fma(nh, U, -zh), bh);
+    dom_mul2_b(ah, __builtin_fma(nh, U, -zh), bh);
   };
   static_assert(PARTIAL % 4 == 2, "five double trips (ping-pong, nothing is copied) and a last single one");
 #pragma unroll 1
@@ -575,11 +777,16 @@ GL_HD bool partial_rounds(uint64_t (&s)[W], Input input, Stop stop) {
   trip(PARTIAL - 2, ol, oh, wl, wh);
   // leave the domain: natural limbs, + what is pending of the constants
   double yl[W], yh[W];
+  if (B_TRI) dom_b_from_tri(wl), dom_b_from_tri(wh);
   dom_leave_d(wl, yl);
   dom_leave_d(wh, yh);
   yl[0] = __builtin_fma(nl, 8.0 * U, yl[0]), yh[0] = __builtin_fma(nh, 8.0 * U, yh[0]);
+  if (SMALL_TOP) {
+    recombine_all_s<TOP0_PLANES>(yl, yh, [&](int k) { return doms_last(k); }, s, 2);
+  } else {
 #pragma unroll
-  for (int k = 0; k < W; k++) s[k] = recombine_d(yl[k], yh[k], domd_last(k));
+    for (int k = 0; k < W; k++) s[k] = recombine_d(yl[k], yh[k], domd_last(k));
+  }
 #endif
   return true;
 }
