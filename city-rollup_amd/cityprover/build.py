@@ -1,77 +1,136 @@
 """Build libcityprover_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU). The library is several
-translation units (csrc/*.hip) compiled in parallel and linked into one shared object."""
+translation units (csrc/*.hip) compiled in parallel and linked into one shared object.
+
+compile_if_needed() is the one place that runs hipcc, for the library, the test twins (tests/simlibs.py) and tools/witgen. It
+asks the compiler what an output depends on (-MD) and keeps, beside the output, <out>.deps.json: the argv and the sha256 of
+the source and of every header in the tree it read. An output is up to date when that manifest still describes the tree;
+modification times play no part."""
+import glob
+import hashlib
+import json
 import os
+import shlex
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SO = os.path.join(PKG, "libcityprover_hip.so")
 OBJ = os.path.join(PKG, "build")
-# translation unit -> the headers it includes (core.h and its own includes are shared by all)
-COMMON = ["core.h", "gl.h", "host_util.h", "dev_pool.h", "dev_mem.h"]
-UNITS = {
-    "cityprover.hip": ["poseidon.h", "poseidon_coop.h", "poseidon_tables.h", "merkle.h", "ntt.h", "ntt16.h", "fri.h", "transcript.h", "zs.h", "quotient.h", "gates.h",
-                       "quotient.inc", "prover_tail.inc", "fri_engine.inc", "fri_prove.inc", "batcher.inc", "verify.inc", "fri_verify.h", "circuit_file.inc", "air.h", "ext3.h", "stark.inc", "check.h", "check.inc"],
-    "bls.hip": ["bls12_381.h", "bls12_381_tables.h", "msm.h", "msm.inc", "bls12_381_fr.h", "fr_ntt.h", "fr_ntt.inc", "groth16.inc",
-                "groth16_pack.inc", "pairing.h", "bls_sqrt.h", "r1cs.h", "r1cs.inc", "fixed_base.h", "fixed_base.inc", "groth16_setup.h", "groth16_setup.inc", "groth16_key.h",
-                "point_ntt.h", "point_ntt.inc", "groth16_srs.h", "groth16_srs.inc"],
-    "pairing.hip": ["bls12_381.h", "bls12_381_tables.h", "bls12_381_fr.h", "pairing.h", "bls_sqrt.h"],
-    "keyfile.hip": ["bls12_381.h", "bls12_381_tables.h", "pairing.h", "bls_sqrt.h", "groth16_key.h"],
-}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function"]
 
 
-def _mtime(path):
-    return os.path.getmtime(path) if os.path.exists(path) else 0.0
+def _hipcc():
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def _unit_stale(unit):
-    obj = os.path.join(OBJ, unit + ".o")
-    if not os.path.exists(obj):
-        return True
-    t = os.path.getmtime(obj)
-    deps = [os.path.join(CSRC, f) for f in [unit] + COMMON + UNITS[unit]]
-    deps.append(os.path.join(os.path.dirname(PKG), "include", "cityprover.h"))
-    return any(_mtime(d) > t for d in deps)
+def _sha(path):
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
+
+
+def _key(argv):
+    """argv as the manifest keeps it: the tree's own location taken out, so a copy of the tree stays up to date"""
+    return [a.replace(ROOT + os.sep, "") for a in argv]
+
+
+def _argv(src, out, flags, mode):
+    return [_hipcc()] + flags + [mode, "-o", out, src]
+
+
+def _fresh(out, argv):
+    """the manifest of `out` if it still describes the tree, else None"""
+    try:
+        with open(out + ".deps.json") as f:
+            m = json.load(f)
+        if os.path.exists(out) and m["argv"] == _key(argv) and all(_sha(os.path.join(os.path.dirname(out), p)) == h for p, h in m["files"].items()):
+            return m
+    except (OSError, ValueError, KeyError):
+        pass
+    return None
+
+
+def _write_manifest(out, argv, files):
+    tmp = "%s.deps.json.%d.tmp" % (out, os.getpid())
+    with open(tmp, "w") as f:
+        json.dump({"argv": _key(argv), "files": files}, f, indent=1, sort_keys=True)
+    os.replace(tmp, out + ".deps.json")
+
+
+def compile_if_needed(src, out, flags, mode, force=False, verbose=False):
+    """hipcc `flags` `mode` (-c or -shared) `src` -o `out`, unless `out` is up to date. Several processes may build the same
+    output at once: private temporary names, the output renamed into place before its manifest. Returns `out`."""
+    if not os.path.exists(os.path.join(CSRC, "poseidon_tables.h")):
+        subprocess.run([sys.executable, os.path.join(CSRC, "gen_tables.py")], check=True)
+    argv = _argv(src, out, flags, mode)
+    if not force and _fresh(out, argv):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    tmp = "%s.%d.tmp" % (out, os.getpid())
+    cmd = argv[:-3] + ["-MD", "-MF", tmp + ".d", "-o", tmp, src]
+    if verbose:
+        print(" ".join(cmd))
+    try:
+        subprocess.run(cmd, check=True)
+        with open(tmp + ".d") as f:
+            deps = shlex.split(f.read().replace("\\\n", " "))[1:]   # make syntax: "target: dep dep \"
+        # the source and the headers of this tree (or beside the source); system and ROCm headers are left out
+        roots = (os.path.realpath(ROOT) + os.sep, os.path.dirname(os.path.realpath(src)) + os.sep)
+        here = os.path.dirname(out)
+        files = {os.path.relpath(d, here): _sha(d) for d in sorted({os.path.realpath(d) for d in deps}) if d.startswith(roots)}
+        os.replace(tmp, out)
+        _write_manifest(out, argv, files)
+    finally:
+        for t in (tmp, tmp + ".d"):
+            if os.path.exists(t):
+                os.remove(t)
+    return out
+
+
+def units():
+    return sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip")))
+
+
+def _obj(unit):
+    return os.path.join(OBJ, unit + ".o")
+
+
+def _link_argv():
+    return [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO] + [_obj(u) for u in units()]
+
+
+def _so_argv():
+    # the library's manifest: every unit's command, then the link's; its files are the units' (objects need not be kept)
+    return sum((_argv(os.path.join(CSRC, u), _obj(u), FLAGS, "-c") for u in units()), []) + _link_argv()
 
 
 def stale():
-    if not os.path.exists(SO):
-        return True
-    return any(_unit_stale(u) or _mtime(os.path.join(OBJ, u + ".o")) > os.path.getmtime(SO) for u in UNITS)
+    return _fresh(SO, _so_argv()) is None
 
 
 def build(force=False, verbose=False):
-    if not os.path.exists(os.path.join(CSRC, "poseidon_tables.h")):
-        subprocess.run([sys.executable, os.path.join(CSRC, "gen_tables.py")], check=True)
     if not force and not stale():
         return SO
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    os.makedirs(OBJ, exist_ok=True)
-    pid = os.getpid()   # several ranks may build at once: private names, atomic renames
-
-    def compile_unit(unit):
-        obj = os.path.join(OBJ, unit + ".o")
-        if not force and not _unit_stale(unit):
-            return obj
-        tmp = "%s.%d.tmp" % (obj, pid)
-        cmd = [hipcc] + FLAGS + ["-c", os.path.join(CSRC, unit), "-o", tmp]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, obj)
-        return obj
-
-    with ThreadPoolExecutor(len(UNITS)) as ex:
-        objs = list(ex.map(compile_unit, UNITS))
-    tmp = "%s.%d.tmp" % (SO, pid)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs
+    with ThreadPoolExecutor(len(units())) as ex:
+        objs = list(ex.map(lambda u: compile_if_needed(os.path.join(CSRC, u), _obj(u), FLAGS, "-c", force, verbose), units()))
+    tmp = "%s.%d.tmp" % (SO, os.getpid())   # several ranks may build at once: private names, atomic renames
+    cmd = _link_argv()
+    cmd[cmd.index(SO)] = tmp
     if verbose:
         print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    os.replace(tmp, SO)
+    try:
+        subprocess.run(cmd, check=True)
+        files = {}
+        for o in objs:
+            with open(o + ".deps.json") as f:
+                files.update({os.path.relpath(os.path.join(OBJ, p), PKG): h for p, h in json.load(f)["files"].items()})
+        os.replace(tmp, SO)
+        _write_manifest(SO, _so_argv(), files)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
     return SO
 
 

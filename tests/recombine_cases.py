@@ -14,7 +14,6 @@ import oracle_lib as O
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "city-rollup_amd", "csrc")
-sys.path.insert(0, os.path.join(HERE, "recombine_sim"))
 sys.path.insert(0, CSRC)
 P = O.P
 EPS = (1 << 32) - 1
@@ -29,8 +28,8 @@ PERMUTE_SEED, PERMUTE_COUNT = 0x5EED0A11, 1 << 16
 
 
 def host_lib(kind="host"):
-    import recombine_sim_build as rb
-    lib = ctypes.CDLL(rb.build(kind))
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("recombine_" + kind))
     lib.rs_top0.restype = ctypes.c_uint32
     lib.rs_recombine.restype = ctypes.c_uint64
     lib.rs_recombine.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int)]

@@ -9,9 +9,7 @@
     transition and tampered proofs are refused; the quotient identity re-checked at zeta in Python over F_p^2.
 Parity of A13 itself stays UNPINNED (no STARK vector in the reference: smartgadget.rs:505-513 asserts digests only)."""
 import ctypes
-import os
 import struct
-import sys
 
 import numpy as np
 import pytest
@@ -20,14 +18,13 @@ import air_programs as A
 import arith_cases as AC
 import oracle_lib as O
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim"))
 P = O.P
 
 
 @pytest.fixture(scope="module")
 def hs():
-    import build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("hostsim"))
     u64p, u32p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)
     lib.hs_air_point.argtypes = [ctypes.c_int, u32p, ctypes.c_size_t, u64p, ctypes.c_size_t, u32p, ctypes.c_uint32, ctypes.c_int] + [u64p] * 6 + [
         ctypes.c_int, u64p, u64p, u64p, u32p, ctypes.c_char_p]

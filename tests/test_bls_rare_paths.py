@@ -3,8 +3,6 @@ the constructions against the restatements, a false positive of the "same x?" fi
 inside a bucket is fixed only here), mul_small over its extremes, and every input builder of tests/test_gpu_bls_rare_paths.py:
 witnesses and shares of planted positions fail here, without a GPU."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -13,15 +11,14 @@ import bls_rare_paths as B
 import oracle_lib as O
 import test_gpu_bls_rare_paths as T
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim"))
 u32p = ctypes.POINTER(ctypes.c_uint32)
 MIN_SHARE = 15 / 16          # at most 1 in 16 planted positions of a case may fall back to random data
 
 
 @pytest.fixture(scope="module")
 def hs():
-    import build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("hostsim"))
     for name in ("hs_bls_g1_loose_step", "hs_bls_g2_loose_step", "hs_bls_g1_loose_out", "hs_bls_g2_loose_out", "hs_bls_lz_k", "hs_bls_lz_maybe_zero"):
         getattr(lib, name).restype = ctypes.c_int
     return lib

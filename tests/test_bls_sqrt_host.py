@@ -3,13 +3,10 @@
 formulas here are written independently: Euler's criterion for "has a root", squaring for "is a root", integer comparison
 for "larger". No GPU."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
 u64p = ctypes.POINTER(ctypes.c_uint64)
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -17,9 +14,8 @@ u8p = ctypes.POINTER(ctypes.c_uint8)
 
 @pytest.fixture(scope="module")
 def ss():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "sqrtsim"))
-    import sqrtsim_build as sb
-    return ctypes.CDLL(sb.build())
+    import simlibs
+    return ctypes.CDLL(simlibs.build("sqrtsim"))
 
 
 def words(*vals):

@@ -54,9 +54,11 @@ def test_every_host_wrapper_has_a_device_twin_or_a_named_exclusion():
 
 
 def test_twins_share_the_element_bodies_and_the_products_flags():
-    build = open(os.path.join(HERE, "devsim", "devsim_build.py")).read()
-    assert re.search(r"^from cityprover\.build import FLAGS\b", build, re.M)
-    assert re.search(r"\+\s*FLAGS\s*\+", build), "the compile line does not use the product's flags"
-    assert not re.search(r"ffast-math|GL_PORTABLE|-O[0-3s]\b", "\n".join(l for l in build.splitlines() if not l.lstrip().startswith(("#", '"""')) and "no -ffast-math" not in l))
+    import cityprover.build
+    import simlibs
+    for p in DEVICE_SOURCES:
+        (flags,) = [f for src, f, _ in simlibs.TWINS.values() if src == p]
+        assert flags is cityprover.build.FLAGS, "%s is not compiled with the product's flags" % p
+        assert not re.search(r"ffast-math|GL_PORTABLE", " ".join(flags))   # the entry is the product's list: no flag, no -O of its own
     for p in HOST_SOURCES + DEVICE_SOURCES:
         assert re.search(r'#include "(\.\./hostsim/)?sim_(gl|bls)\.h"', open(os.path.join(HERE, p)).read()), p

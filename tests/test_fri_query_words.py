@@ -111,11 +111,8 @@ def case(name):
 
 @pytest.fixture(scope="module")
 def vh():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("verify_hostsim_build", os.path.join(HERE, "verify_hostsim", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    lib = ctypes.CDLL(mod.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("verify_hostsim"))
     lib.vh_instance_size.restype = ctypes.c_size_t
     lib.vh_query_phase_many.restype = None
     lib.vh_query_phase_many.argtypes = [ctypes.POINTER(V.Instance), _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t, _u64p, ctypes.c_size_t,

@@ -74,10 +74,8 @@ GATE_IDS = [S.NAME[g[0]] for g in S.ALL_GATES]
 # ---- the evaluators ----
 class GateSim:
     def __init__(self):
-        import sys
-        sys.path.insert(0, os.path.join(HERE, "gatesim"))
-        import gatesim_build
-        self.L = ctypes.CDLL(gatesim_build.build())
+        import simlibs
+        self.L = ctypes.CDLL(simlibs.build("gatesim"))
         for name in ("gs_num_constraints", "gs_num_wires", "gs_num_constants", "gs_eval_base", "gs_eval_ext"):
             getattr(self.L, name).restype = ctypes.c_int
 

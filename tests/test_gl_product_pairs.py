@@ -5,8 +5,6 @@ the CPU: every class and corner of the product chain in slot A against every one
 (both) on the partners of every first-round pair. CPU only."""
 import collections
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -15,7 +13,6 @@ import product_chain as C
 import product_pairs as PP
 import rare_paths as R
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "pairs_hostsim"))
 P = C.P
 p64 = ctypes.POINTER(ctypes.c_uint64)
 
@@ -26,8 +23,8 @@ def ptr(x):
 
 @pytest.fixture(scope="module")
 def hs():
-    import pairs_hostsim_build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("pairs_hostsim"))
     lib.pairs_mul_lazy2.argtypes = [p64] * 8 + [ctypes.c_size_t]
     lib.pairs_sbox.argtypes = [p64] * 4 + [ctypes.c_size_t]
     return lib

@@ -5,8 +5,6 @@ every class in slot A against every class in slot B (neither repairs, only A, on
 form that `diff_times_w16` produces, in both directions. The operand arrays (tests/ntt_pair_cases.py) are the ones
 tests/test_gpu_ntt_pairs.py feeds to the device. CPU only."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -15,7 +13,6 @@ import ntt_pair_cases as NP
 import product_pairs as PP
 import rare_paths as R
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "ntt_pairs_hostsim"))
 P = R.P
 p64 = ctypes.POINTER(ctypes.c_uint64)
 
@@ -30,8 +27,8 @@ def canon(x):
 
 @pytest.fixture(scope="module")
 def hs():
-    import ntt_pairs_hostsim_build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("ntt_pairs_hostsim"))
     lib.np_reduce2.argtypes = [p64] * 10 + [ctypes.c_size_t]
     lib.np_mul2.argtypes = [p64] * 8 + [ctypes.c_size_t]
     lib.np_pow2_2.argtypes = [ctypes.c_int, ctypes.c_int] + [p64] * 6 + [ctypes.c_size_t]

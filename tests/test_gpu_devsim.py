@@ -18,8 +18,6 @@ import product_chain as C
 import rare_paths as R
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-for d in ("devsim", "hostsim", "renorm_hostsim"):
-    sys.path.insert(0, os.path.join(HERE, d))
 pytestmark = pytest.mark.gpu
 P, M64, EPS = AC.P, AC.M64, AC.EPS
 CHUNK = 2048
@@ -33,13 +31,11 @@ class Libs:
 
 @pytest.fixture(scope="module")
 def L():
-    import build as hostsim_build
-    import devsim_build
-    import renorm_hostsim_build
-    so = devsim_build.build()
+    import simlibs
+    so = simlibs.build_all(["devsim_gl", "devsim_bls"])
     lib = Libs()
-    lib.gl, lib.bls = ctypes.CDLL(so["gl"]), ctypes.CDLL(so["bls"])
-    lib.hs, lib.rn = ctypes.CDLL(hostsim_build.build()), ctypes.CDLL(renorm_hostsim_build.build())
+    lib.gl, lib.bls = ctypes.CDLL(so["devsim_gl"]), ctypes.CDLL(so["devsim_bls"])
+    lib.hs, lib.rn = ctypes.CDLL(simlibs.build("hostsim")), ctypes.CDLL(simlibs.build("renorm_hostsim"))
     u64, u32, dbl = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_double
     for name, args in (("hs_mul", [u64] * 2), ("hs_mul_lazy", [u64] * 2), ("hs_add", [u64] * 2), ("hs_sub", [u64] * 2), ("hs_gl_op1", [ctypes.c_int, u64]),
                        ("hs_gl_op2", [ctypes.c_int, u64, u64]), ("hs_mul_add_lazy", [u64] * 3), ("hs_fold_top", [u64, u32]),

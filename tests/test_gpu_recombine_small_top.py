@@ -19,8 +19,8 @@ N = 320                                        # five waves over two workgroups,
 
 @pytest.fixture(scope="module")
 def libs():
-    import recombine_sim_build as rb
-    dev = ctypes.CDLL(rb.build("device"))
+    import simlibs
+    dev = ctypes.CDLL(simlibs.build("recombine_device"))
     dev.rsd_site.argtypes = [ctypes.c_int, ctypes.c_int, pd, pd, p64, ctypes.c_size_t]
     return RC.host_lib("host"), dev, RC.wanted_constants()
 

@@ -206,9 +206,8 @@ CLASS_CODE = {"flag": 1, "range": 2, "no_point": 3}      # the classes a point h
 @pytest.fixture(scope="module")
 def ks():
     import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests", "keyfilesim"))
-    import keyfilesim_build as kb
-    lib = ctypes.CDLL(kb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("keyfilesim"))
     for f in (lib.ks_unpack_g1, lib.ks_unpack_g2):
         f.argtypes, f.restype = [u8p, ctypes.c_int, u64p, ctypes.POINTER(ctypes.c_int)], ctypes.c_int
     for f in (lib.ks_pack_g1, lib.ks_pack_g2):

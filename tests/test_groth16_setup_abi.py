@@ -6,7 +6,6 @@ built for the CPU)."""
 import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -78,9 +77,8 @@ def test_ctypes_mirrors_have_the_sizes_the_c_compiler_gives(tmp_path):
 # ---- the host-callable code of the feature on the CPU (tests/setupsim) ------------------------------------------------------
 @pytest.fixture(scope="module")
 def ss():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "setupsim"))
-    import setupsim_build as sb
-    lib = ctypes.CDLL(sb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("setupsim"))
     lib.ss_recode.argtypes = [u64p, ctypes.POINTER(ctypes.c_int32)]
     lib.ss_transpose.argtypes = [u64p, u32p, u32p, ctypes.c_size_t, ctypes.c_size_t, u64p, u32p, u32p]
     return lib

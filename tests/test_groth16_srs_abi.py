@@ -6,7 +6,6 @@ butterfly, twiddle and bit-reversal indexing of the transform - agree with the o
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -80,9 +79,8 @@ def test_null_arguments_give_a_status_and_a_message():
 # ---- the host-callable code of the kernels on the CPU (tests/pointsim) ------------------------------------------------------
 @pytest.fixture(scope="module")
 def ps():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "pointsim"))
-    import pointsim_build as pb
-    lib = ctypes.CDLL(pb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("pointsim"))
     for f in (lib.ps_g1_mul, lib.ps_g2_mul):
         f.argtypes = [ctypes.c_int, u64p, ctypes.c_int, u64p, u64p]
     lib.ps_top_bit.argtypes = [u64p]

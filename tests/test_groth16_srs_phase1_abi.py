@@ -7,7 +7,6 @@ tests/test_groth16_srs_abi.py already holds against the oracle on its own; here 
 import ctypes
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
@@ -66,9 +65,8 @@ def test_null_arguments_give_a_status_and_a_message():
 # ---- the per-lane code of k_scale_each on the CPU (tests/srsphase1sim) -----------------------------------------------------
 @pytest.fixture(scope="module")
 def sim():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "srsphase1sim"))
-    import srsphase1sim_build as sb
-    lib = ctypes.CDLL(sb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("srsphase1sim"))
     lib.sp_each_scalar.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, u64p, u64p, u64p, u64p]
     lib.sp_each_scalar.restype = None
     for f in (lib.sp_g1_lane, lib.sp_g2_lane):

@@ -1,8 +1,6 @@
 """The device arithmetic (city-rollup_amd/csrc/*.h, __host__ __device__) instantiated on the host
 and checked against the oracle: lazy reductions, limb-plane MDS, full permutation. CPU only."""
 import ctypes
-import os
-import sys
 from fractions import Fraction
 
 import numpy as np
@@ -11,14 +9,13 @@ import pytest
 import arith_cases as AC
 import oracle_lib as O
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim"))
 P = O.P
 
 
 @pytest.fixture(scope="module")
 def hs():
-    import build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("hostsim"))
     u64 = ctypes.c_uint64
     for f in ("hs_mul", "hs_mul_lazy", "hs_add", "hs_sub"):
         getattr(lib, f).restype = u64

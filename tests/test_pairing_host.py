@@ -2,8 +2,6 @@
 kernels run, built for the host) against Python integers (tests/pairing_ref.py, which shares no formula with it), and the
 reference's own sanity. No GPU."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,16 +9,14 @@ import pytest
 import pairing_cases as PC
 import pairing_ref as PR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, R = PR.P, PR.R
 u64p = ctypes.POINTER(ctypes.c_uint64)
 
 
 @pytest.fixture(scope="module")
 def ps():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "pairingsim"))
-    import pairingsim_build as pb
-    return ctypes.CDLL(pb.build())
+    import simlibs
+    return ctypes.CDLL(simlibs.build("pairingsim"))
 
 
 def ptr(a):

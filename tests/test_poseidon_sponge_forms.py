@@ -1,15 +1,12 @@
 """The sponge-aware forms of the permutation (poseidon.h `permute_until<OUT, ZERO_CAP>`: which outputs are kept, whether the
 capacity comes in as zero) on the host: every live word equals `permute_textbook`'s. CPU only."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "sponge_hostsim"))
 P = O.P
 OUT_ALL, OUT_CAPACITY, OUT_DIGEST = 0, 1, 2
 LIVE = {OUT_ALL: slice(0, 12), OUT_CAPACITY: slice(8, 12), OUT_DIGEST: slice(0, 4)}
@@ -19,8 +16,8 @@ M64 = (1 << 64) - 1
 
 @pytest.fixture(scope="module")
 def hs():
-    import sponge_hostsim_build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("sponge_hostsim"))
     lib.hs_sponge_permute.argtypes = [p64, ctypes.c_size_t, ctypes.c_int, ctypes.c_int]
     lib.hs_sponge_node.argtypes = [p64, ctypes.c_uint64, p64]
     lib.hs_sponge_textbook.argtypes = [p64, ctypes.c_size_t]

@@ -4,7 +4,6 @@ kernels share (the one-limb multiplication, the limb split) agrees with Python i
 import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -70,9 +69,8 @@ def test_ctypes_mirrors_have_the_sizes_the_c_compiler_gives(tmp_path):
 # ---- the arithmetic of the kernels on the host (tests/r1cs_hostsim: the __host__ __device__ functions of csrc/r1cs.h) ----------
 @pytest.fixture(scope="module")
 def hs():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "r1cs_hostsim"))
-    import r1cs_hostsim_build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("r1cs_hostsim"))
     u64p = ctypes.POINTER(ctypes.c_uint64)
     lib.hs_r1cs_mul_small.argtypes = [u64p, ctypes.c_uint32, u64p]
     lib.hs_r1cs_term.argtypes = [u64p, u64p, u64p, u64p]

@@ -2,8 +2,6 @@
 inverse Poseidon permutation against the oracle, the operand constructors, and every input builder of
 tests/test_gpu_rare_paths.py (shapes and witnesses fail here, without a GPU)."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ import oracle_lib as O
 import rare_paths as R
 import test_gpu_rare_paths as T
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim"))
 P = O.P
 M = (1 << 64) - 1
 p64 = ctypes.POINTER(ctypes.c_uint64)
@@ -20,8 +17,8 @@ p64 = ctypes.POINTER(ctypes.c_uint64)
 
 @pytest.fixture(scope="module")
 def hs():
-    import build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("hostsim"))
     lib.hs_mul_paths.restype = ctypes.c_int
     lib.hs_mul_paths.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     lib.hs_mul_pow2.restype = ctypes.c_uint64

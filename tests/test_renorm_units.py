@@ -13,7 +13,6 @@ import pytest
 
 import oracle_lib as O
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "renorm_hostsim"))
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "city-rollup_amd", "csrc")
 P = O.P
@@ -28,8 +27,8 @@ from arith_cases import BOUND, LIM, U, absorb_chunks, exact_renorm32, input_stat
 
 @pytest.fixture(scope="module")
 def hs():
-    import renorm_hostsim_build as hb
-    lib = ctypes.CDLL(hb.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("renorm_hostsim"))
     lib.hs_rn_renorm.argtypes = [ctypes.c_int, pd, pd]
     lib.hs_rn_recombine.restype = ctypes.c_uint64
     lib.hs_rn_recombine.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int]

@@ -20,11 +20,8 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 
 @pytest.fixture(scope="module")
 def vh():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("verify_hostsim_build", os.path.join(HERE, "verify_hostsim", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    lib = ctypes.CDLL(mod.build())
+    import simlibs
+    lib = ctypes.CDLL(simlibs.build("verify_hostsim"))
     lib.vh_instance_size.restype = ctypes.c_size_t
     lib.vh_check_path.argtypes = [_u64p, ctypes.c_uint32, ctypes.c_uint64, _u64p, ctypes.c_uint32, _u64p, ctypes.c_uint32]
     lib.vh_query_phase.restype = ctypes.c_uint32

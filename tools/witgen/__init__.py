@@ -1,7 +1,7 @@
 """ctypes loader for the bench-side witness helper (tools/witgen/witgen.hip)."""
 import ctypes
 import os
-import subprocess
+import sys
 
 import numpy as np
 
@@ -11,15 +11,10 @@ _lib = None
 
 
 def build():
-    """Compile libwitgen.so if missing or stale. Several ranks may get here at once: build to a private name, then
-    rename atomically."""
-    src = os.path.join(HERE, "witgen.hip")
-    if not os.path.exists(SO) or os.path.getmtime(src) > os.path.getmtime(SO):
-        tmp = "%s.%d.tmp" % (SO, os.getpid())
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-shared", "-fPIC",
-                        "-Wno-unused-value", "-o", tmp, src], check=True)
-        os.replace(tmp, SO)
-    return SO
+    """Compile libwitgen.so if missing or stale (cityprover.build.compile_if_needed; several ranks may get here at once)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "city-rollup_amd"))
+    from cityprover.build import compile_if_needed
+    return compile_if_needed(os.path.join(HERE, "witgen.hip"), SO, ["--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-Wno-unused-value"], "-shared")
 
 
 def lib():
